@@ -18,11 +18,15 @@ torch.distributed.run BEFORE anything touches the GPU) every step ends with the 
 trainer -- ONE all-reduce of the flat 165 MB fp32 gradient bucket of RepDepth (mal_amd/dp.py; manydepth/trainer.py:
 309-311,469) -- timed inside the step and reported as its own `breakdown_ms` entry.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does nothing else: it sets up, warms up, times the
+--steps steps and prints the line.  `--full` adds every side measurement, each in extra work after the timed steps:
   roofline:     the teacher-pass fused kernel, timed live with HIP events on its stream (--mode step only)
   cpu_baseline: the CPU oracle (PyTorch-CPU restatement == the reference's path) on the host
   train_step:   the WHOLE training step of the harness (networks through MIOpen + this loss path + all-reduce + Adam):
                 images/s and per-stage breakdown, so that the loss-path rate in `value` is never read as training throughput.
+  and the warm regime, the eager step, the stage breakdown, the overlapped exchange (N>1) and the channels_last variant.
+`--dump-outputs DIR` writes what the last timed step handed its caller (the loss dictionary and the leaves' gradients) as
+DIR/<name>.npy; the same arguments give the timed steps the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -104,6 +108,11 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed CPU-oracle steps (median), after 3 warm-ups")
     ap.add_argument("--train-steps", type=int, default=20,
                     help="steps of the whole training step timed for the `train_step` block after 3 warm-ups (0 = leave it out)")
+    ap.add_argument("--full", action="store_true",
+                    help="every side measurement after the timed steps (warm regime, eager step, breakdown, roofline, "
+                         "channels_last, train_step, cpu_baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss dictionary, leaf gradients) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -153,6 +162,37 @@ def spawn_ranks(args):
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
+OUTPUT_BYTES_CAP = 64 << 20  # --dump-outputs: larger outputs are written as a fixed, seeded sample of their elements
+
+
+def host_outputs(st):
+    """what the caller of the timed path received from `st`'s last step, on the host: the tensors of its loss dictionary and,
+    for a loss step, the gradients of its leaves"""
+    out = {"loss." + str(k): v for k, v in st.losses.items() if torch.is_tensor(v)}
+    for k, v in getattr(st, "leaves", {}).items():
+        if v.grad is not None:
+            out["grad." + k] = v.grad
+    return {k: v.detach().cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(d, arrays):
+    """DIR/<name>.npy in float32 (float64 stays float64), at most OUTPUT_BYTES_CAP in all"""
+    import re
+    import numpy as np
+    arrays = {k: np.asarray(a, dtype=np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32)
+              for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = OUTPUT_BYTES_CAP - 256 * len(arrays)  # room for the .npy headers
+    rng = np.random.default_rng(0)
+    os.makedirs(d, exist_ok=True)
+    for k in sorted(arrays):
+        a = arrays[k]
+        if total > budget and a.size > 1:
+            n = max(1, int(a.size * budget // total))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, n, replace=False))]
+        np.save(os.path.join(d, re.sub(r"[^A-Za-z0-9_.-]+", "_", k) + ".npy"), a)
+
+
 class TrainStep:
     """--mode train: mal_amd.harness.TrainHarness on a synthetic batch (next row N1; not the headline metric)."""
 
@@ -174,7 +214,8 @@ class TrainStep:
         self.batch_cpu = None
 
     def __call__(self):
-        return self.h.train_step(self.inputs)["loss"]
+        self.losses = self.h.train_step(self.inputs)
+        return self.losses["loss"]
 
     def breakdown_ms(self, steps=5):
         """mean device time per stage over a few extra steps outside the timed region"""
@@ -281,6 +322,7 @@ class Step:
             losses, _, _ = self.step_mod.loss_step(self.lp.opt, self.inputs, mono_outputs, outputs, want_maps=False,
                                                    image_synthesis=self.synth)
             losses["loss"].backward(gradient=self.one)
+            self.losses = losses
             return losses["loss"]
         if self.mode == "multiscale":  # trainer.py:573-612 with not opt.distil, both networks, four scales: one call
             mono_outputs = {("disp", 0): lv["disp_teacher"]}
@@ -295,6 +337,7 @@ class Step:
             losses, _ = self.step_mod.loss_step_multiscale(self.lp.opt, self.inputs, mono_outputs, outputs, want_maps=False,
                                                            image_synthesis=self.synth)
             losses["loss"].backward(gradient=self.one)
+            self.losses = losses
             return losses["loss"]
         self.ops.clear_packed_sources()  # a real step sees new images: repack them every step
         T_m1 = L.transformation_from_parameters(lv["axisangle_m1"], lv["translation_m1"], True)
@@ -315,6 +358,7 @@ class Step:
             else:            # mal_dr_loss_fwd/_bwd: one library call per direction
                 losses = self.lp.loss_step(self.inputs, outputs)
             losses["loss"].backward(gradient=self.one)
+            self.losses = losses
             return losses["loss"]
         mono_outputs = {("disp", 0): lv["disp_teacher"], ("cam_T_cam", 0, -1): T_m1, ("cam_T_cam", 0, 1): T_p1}
         outputs = {("disp", 0): lv["disp_student"], ("cam_T_cam", 0, -1): T_m1, ("cam_T_cam", 0, 1): T_p1,
@@ -333,9 +377,13 @@ class Step:
             losses, _ = lp.compute_losses(self.inputs, outputs, is_multi=True)
             total = losses["loss"] + mono_losses["loss"]
             total.backward()
+            self.losses = {"mono/%s" % (k,): v for k, v in mono_losses.items()}
+            self.losses.update(losses)
+            self.losses["total"] = total
             return total
         _, losses, _ = self.lp.compute_batch_losses(self.inputs, mono_outputs, outputs)
         losses["loss"].backward()
+        self.losses = losses
         return losses["loss"]
 
 
@@ -720,14 +768,23 @@ def main():
         for _ in range(20):
             one_pass()
         torch.cuda.synchronize()
+    # the ramp's length follows the clock: end it on a whole rotation and restart the tie-break noise streams, so that the
+    # same arguments hand the timed steps the same batches and the same noise in every run (--dump-outputs compares runs)
+    if rot is not None:
+        while rot.i % R:
+            rot()
+        torch.cuda.synchronize()
+        from mal_amd import step as step_mod
+        step_mod.noise_counter(dev).zero_()
+        torch.cuda.manual_seed(1234 + rank)
     for _ in range(args.warmup):
         run()
-    # HIP events around the teacher-pass kernel (the first marching launch of a step), eager only
+    # HIP events around the teacher-pass kernel (the first marching launch of a step), eager --full runs only
     ev = []
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if graph is None and args.mode in ("step", "distil"):
+        if args.full and graph is None and args.mode in ("step", "distil"):
             a, b_ = lib.mal_event_create(), lib.mal_event_create()
             lib.mal_profile_next_pass(a, b_)
             ev.append((a, b_))
@@ -740,11 +797,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         n_ranks = dist.get_world_size()  # the ranks the collective actually saw
+    # what the last timed step returned, read before any side measurement runs the step objects again
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = host_outputs(rot.steps[(rot.i - 1) % R] if rot is not None else step)
 
     # the WARM regime beside the line (rounds 1-4 reported this one): batch 0 replayed over and over, its ~100 MB working set
     # resident in the 256 MiB Infinity Cache
     warm_ms = None
-    if both and rot is not None:
+    if args.full and both and rot is not None:
         n_w = max(args.steps, 100)
         for _ in range(20):
             rot.first()
@@ -758,7 +819,7 @@ def main():
     # the same step as eager launches (what a trainer whose producer cannot be captured into a graph would see: the
     # real producer calls two external models with a data-dependent number of instances between the library calls)
     eager_ms = None
-    if graph is not None:
+    if args.full and graph is not None:
         n_e = max(args.steps, 50)
         for _ in range(5):
             eager_pass()
@@ -773,7 +834,7 @@ def main():
 
     # stages of the step, device time (HIP events on the current stream), outside the timed region
     breakdown = None
-    if args.mode != "train":
+    if args.full and args.mode != "train":
         n_bd = 20
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         acc = [0.0, 0.0]
@@ -793,7 +854,7 @@ def main():
     # flight on RCCL's stream while step k+1 computes -- how DDP hides it behind the backward (manydepth/trainer.py:469);
     # the loss path alone offers nothing else to hide 165 MB behind.  Reported as its own block, never as `value`.
     overlapped = None
-    if bucket is not None:
+    if args.full and bucket is not None:
         try:
             work = None
             sync()
@@ -817,7 +878,7 @@ def main():
             overlapped = {"error": "%s: %s" % (type(ex).__name__, str(ex).splitlines()[0][:200])}
 
     durs = []
-    if args.mode in ("step", "distil"):
+    if args.full and args.mode in ("step", "distil"):
         if graph is not None:  # kernel timing needs eager launches: a few extra steps outside the timed region
             for i in range(20):
                 a, b_ = lib.mal_event_create(), lib.mal_event_create()
@@ -836,7 +897,7 @@ def main():
     # (cold regime: 8 of them; warm: 1), first by events around eager launches, then replayed from a graph of nothing else
     kern_ms_plain = kern_ms
     replayed = replayed_warm = None
-    if args.mode in ("step", "distil"):
+    if args.full and args.mode in ("step", "distil"):
         R_k = (8 if R >= 6 else R) if cold else 1  # (a reduced --rotate, as the quick tests use, reduces this rotation too)
         plains = Rotation(dev, 1234 + rank + 104729, "distil", R_k, slot_base=300, graph=False)
         pev = []
@@ -866,7 +927,7 @@ def main():
         del plains
 
     cl_block = None
-    if args.mode in ("step", "distil") and not args.channels_last and rank == 0:
+    if args.full and args.mode in ("step", "distil") and not args.channels_last and rank == 0:
         try:
             cl_block = channels_last_block(dev, 1234 + rank, args.mode, R)
         except Exception as ex:
@@ -888,8 +949,9 @@ def main():
     # sits in `train_step` at every N, and `scaling_quantity` names the field the DP-scaling ratio is to be taken from)
     value_is_train = args.mode == "step" and args.value == "train"
     train_block = None
-    if args.mode != "train" and (args.train_steps > 0 or value_is_train):
+    if args.mode != "train" and ((args.full and args.train_steps > 0) or value_is_train):
         def train_side_block():
+            nonlocal outputs
             n_train, n_warm = (args.steps, max(args.warmup, 1)) if value_is_train else (args.train_steps, 3)
             ts = TrainStep(dev, 1234 + rank)
             for _ in range(n_warm):
@@ -900,6 +962,8 @@ def main():
                 ts()
             sync()
             dtt = time.perf_counter() - t1
+            if value_is_train and args.dump_outputs and rank == 0:  # the line's timed path is this one
+                outputs = host_outputs(ts)
             if dist is not None:
                 t = torch.tensor([dtt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -985,7 +1049,7 @@ def main():
         out["breakdown_ms"] = breakdown
     if overlapped is not None:
         out["exchange_overlapped"] = overlapped
-    if args.mode in ("step", "distil"):
+    if args.full and args.mode in ("step", "distil"):
         # kernel_ms / achieved / frac: the kernel inside a REPLAYED graph (what the headline's graph-replayed step runs),
         # measured in this run; eager_kernel_ms: the same kernel bracketed by HIP events on eager launches (6-10 % longer:
         # an eager stream's packets carry release fences, and the event pair adds packet processing; LABBOOK.md 5)
@@ -1050,7 +1114,8 @@ def main():
                                      "B=12 per GPU, 192x640, --distil, synthetic batch, random-init weights")
         out["config"]["parallelism"] = "dp%d (one RCCL all-reduce of the flat gradient bucket per step)" % n_ranks
         out["config"]["api"] = "mal_amd.harness.TrainHarness.train_step"
-        out["breakdown_ms"] = step.breakdown_ms()
+        if args.full:
+            out["breakdown_ms"] = step.breakdown_ms()
         out["exchange"] = step.h.exchange_note()
     elif args.mode in ("dualrefine", "dualrefine_ops"):
         out["config"]["workload"] = ("DualRefine+MAL loss loops, B=8 per GPU, 192x640 (BASELINE configs[4]): generate_images_pred + "
@@ -1100,7 +1165,7 @@ def main():
         out["config"]["launch"] = "eager (host-side RNG, optimizer and collective in the step)"
         out["config"]["api"] = "mal_amd.harness.TrainHarness.train_step"
         out["value_is"] = "train_step (--value train): the line's value / ms_per_step are the whole training step's"
-    if n_ranks == 1 and not args.no_cpu_baseline:
+    if args.full and n_ranks == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(batch_cpu, args.cpu_steps, temporal=args.mode in ("step", "temporal"), seed=1234 + rank)
     if W != 640:  # --width: the strings above are written for the headline size
         def resize(o):
@@ -1111,6 +1176,8 @@ def main():
             return o
         out = resize(out)
         out["config"]["width"] = W
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -10,7 +10,7 @@ tail -2 gpurun_out/r05e/fwd_lean_tests.txt
 for rep in 1 2; do
 for v in 0 1; do
   for mode in step distil; do
-  python bench.py --mode $mode --opt fwd_lean=$v --no-cpu-baseline --train-steps 0 --steps 200 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --mode $mode --opt fwd_lean=$v --no-cpu-baseline --train-steps 0 --steps 200 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('$mode fwd_lean=$v', 'cold', round(d['ms_per_step'],4), 'warm', round(d['warm_ms_per_step'],4))" >> $out

@@ -5,7 +5,7 @@ O=gpurun_out/ab_halo; mkdir -p $O
 for round in 1 2; do
   for h in 0 1; do
     for mode in distil step; do
-      python bench.py --mode $mode --steps 400 --warmup 50 --no-cpu-baseline --train-steps 0 --opt march_halo1=$h 2>/dev/null \
+      python bench.py --full --mode $mode --steps 400 --warmup 50 --no-cpu-baseline --train-steps 0 --opt march_halo1=$h 2>/dev/null \
         | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('halo1=$h', '$mode', 'ms/step', round(d['ms_per_step'],4), 'teacher kernel us (events, eager)', round(d['roofline']['kernel_ms']*1e3,1), 'temporal sweep us', round(d.get('roofline_temporal',{}).get('kernel_ms',0)*1e3,1))" || exit 1
     done
   done

@@ -8,7 +8,7 @@ for round in 1 2; do
   for v in "$@"; do
     if [ "$v" = default ]; then unset MAL_HIP_LIB; else export MAL_HIP_LIB=$PWD/mal_amd/lib/$v.so; fi
     for mode in $modes; do
-      python bench.py --mode $mode --steps 300 --warmup 30 --no-cpu-baseline --train-steps 0 2>/dev/null \
+      python bench.py --full --mode $mode --steps 300 --warmup 30 --no-cpu-baseline --train-steps 0 2>/dev/null \
         | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$v', '$mode', 'ms/step', round(d['ms_per_step'],4), 'teacher replayed us', round(r['kernel_ms']*1e3,2), 'eager us', round(r['eager_kernel_ms']*1e3,2), 'frac', round(r['frac'],4))" || exit 1
     done
   done

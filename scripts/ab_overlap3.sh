@@ -7,7 +7,7 @@ out=gpurun_out/r05e/ab_overlap3.txt
 : > $out
 for rep in 1 2; do
 for v in 1 3; do
-  python bench.py --mode step --opt step_overlap=$v --no-cpu-baseline --train-steps 0 --steps 200 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --mode step --opt step_overlap=$v --no-cpu-baseline --train-steps 0 --steps 200 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('step_overlap=$v', 'cold', round(d['ms_per_step'],4), 'warm', round(d['warm_ms_per_step'],4))" >> $out

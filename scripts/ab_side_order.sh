@@ -6,7 +6,7 @@ out=gpurun_out/r05g/ab_side_order.txt
 : > $out
 for rep in 1 2; do
 for v in 0 1; do
-  python bench.py --mode step --opt side_order=$v --no-cpu-baseline --train-steps 0 --steps 300 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --mode step --opt side_order=$v --no-cpu-baseline --train-steps 0 --steps 300 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('side_order=$v', 'cold', round(d['ms_per_step'],4), 'warm', round(d['warm_ms_per_step'],4))" >> $out

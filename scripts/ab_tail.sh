@@ -6,7 +6,7 @@ out=gpurun_out/r05f/ab_tail.txt
 : > $out
 for rep in 1 2 3; do
 for v in 0 1; do
-  python bench.py --mode step --opt tail_overlap=$v --no-cpu-baseline --train-steps 0 --steps 300 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --mode step --opt tail_overlap=$v --no-cpu-baseline --train-steps 0 --steps 300 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('tail_overlap=$v', 'cold', round(d['ms_per_step'],4), 'warm', round(d['warm_ms_per_step'],4), 'channels_last cold', d.get('channels_last',{}).get('ms_per_step'))" >> $out

@@ -3,7 +3,7 @@
 # 512 = S, 1024 = G; results are then wrong, only the time means something) and with longer tasks (march_rows)
 O=gpurun_out/${1:-m3probe}; mkdir -p $O
 run() {
-  timeout -k 10 200 python bench.py --mode distil --steps 100 --warmup 20 --no-cpu-baseline --train-steps 0 "$@" 2>/dev/null \
+  timeout -k 10 200 python bench.py --full --mode distil --steps 100 --warmup 20 --no-cpu-baseline --train-steps 0 "$@" 2>/dev/null \
     | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$*', 'ms/step', round(d['ms_per_step'],4), 'teacher us', round(d['roofline']['kernel_ms']*1e3,1))"
 }
 {

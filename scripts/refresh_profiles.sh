@@ -7,9 +7,9 @@ O=$R/gpurun_out/refresh
 mkdir -p $O
 # the driver's own command, default flags (round 2 lost its headline because this exact line was never run after an edit)
 cd $R && python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit 1
-python bench.py --loss-blc > $O/bench.json 2> $O/bench.err || exit 1
-python bench.py --mode distil --train-steps 0 > $O/bench_distil.json 2> $O/bench_distil.err || exit 1
-python bench.py --mode multiscale --train-steps 0 --no-cpu-baseline > $O/bench_multiscale.json 2> $O/bench_multiscale.err || exit 1
+python bench.py --full --loss-blc > $O/bench.json 2> $O/bench.err || exit 1
+python bench.py --full --mode distil --train-steps 0 > $O/bench_distil.json 2> $O/bench_distil.err || exit 1
+python bench.py --full --mode multiscale --train-steps 0 --no-cpu-baseline > $O/bench_multiscale.json 2> $O/bench_multiscale.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --no-cpu-baseline --train-steps 0 > $O/stats.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_distil -o s -- python3 $R/bench.py --mode distil --no-cpu-baseline --train-steps 0 > $O/stats_distil.log 2>&1 || exit 1

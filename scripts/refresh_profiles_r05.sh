@@ -5,14 +5,14 @@ R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r05r; mkdir -p $O
 cd $R
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit 1
 echo "driver line done" >> $O/progress.log
-python bench.py --loss-blc > $O/bench.json 2> $O/bench.err || exit 1
-python bench.py --mode distil --train-steps 0 > $O/bench_distil.json 2> $O/bench_distil.err || exit 1
+python bench.py --full --loss-blc > $O/bench.json 2> $O/bench.err || exit 1
+python bench.py --full --mode distil --train-steps 0 > $O/bench_distil.json 2> $O/bench_distil.err || exit 1
 echo "bench lines done" >> $O/progress.log
-python bench.py --mode multiscale --train-steps 0 --no-cpu-baseline > $O/bench_multiscale.json 2> $O/bench_multiscale.err || exit 1
-python bench.py --mode multiscale --ms-temporal --train-steps 0 --no-cpu-baseline > $O/bench_multiscale_temporal.json 2> $O/bench_multiscale_temporal.err || exit 1
-python bench.py --mode dualrefine --train-steps 0 --no-cpu-baseline > $O/bench_dualrefine.json 2> $O/bench_dualrefine.err || exit 1
-python bench.py --main-temporal --train-steps 0 --no-cpu-baseline > $O/bench_main_temporal.json 2> $O/bench_main_temporal.err || exit 1
-python bench.py --width 512 --train-steps 0 --no-cpu-baseline > $O/bench_cityscapes.json 2> $O/bench_cityscapes.err || exit 1
+python bench.py --full --mode multiscale --train-steps 0 --no-cpu-baseline > $O/bench_multiscale.json 2> $O/bench_multiscale.err || exit 1
+python bench.py --full --mode multiscale --ms-temporal --train-steps 0 --no-cpu-baseline > $O/bench_multiscale_temporal.json 2> $O/bench_multiscale_temporal.err || exit 1
+python bench.py --full --mode dualrefine --train-steps 0 --no-cpu-baseline > $O/bench_dualrefine.json 2> $O/bench_dualrefine.err || exit 1
+python bench.py --full --main-temporal --train-steps 0 --no-cpu-baseline > $O/bench_main_temporal.json 2> $O/bench_main_temporal.err || exit 1
+python bench.py --full --width 512 --train-steps 0 --no-cpu-baseline > $O/bench_cityscapes.json 2> $O/bench_cityscapes.err || exit 1
 echo "mode lines done" >> $O/progress.log
 cd /tmp && export TMPDIR=/tmp
 for regime in cold warm; do

@@ -6,7 +6,7 @@
 #   scripts/build_variant.py w3 -DMAL_PROBE_W3 && scripts/w3_probe.sh
 run() {  # name lib rows
   if [ "$2" = default ]; then unset MAL_HIP_LIB; else export MAL_HIP_LIB=$PWD/mal_amd/lib/$2.so; fi
-  python bench.py --mode distil --regime warm --steps 200 --warmup 20 --no-cpu-baseline --train-steps 0 --opt march_rows=$3 2>/dev/null \
+  python bench.py --full --mode distil --regime warm --steps 200 --warmup 20 --no-cpu-baseline --train-steps 0 --opt march_rows=$3 2>/dev/null \
     | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print('$1 rows=$3', 'teacher replayed us', round(r['kernel_ms']*1e3,2), 'frac', round(r['frac'],4), '--distil ms/step', round(d['ms_per_step'],4))" || exit 1
 }
 for round in 1 2; do

@@ -1,12 +1,13 @@
 """The driver's own command, run as a child process on the GPU box: `python bench.py --gpus 1 --steps K --warmup W` with
-NO other flags must exit 0 and print ONE JSON line that carries the contract fields, the roofline block (HBM fraction
-and the vector-ALU bound) and the CPU baseline.  Round 2 lost its headline to a bench.py edit that was never run with
-the default arguments; this test is that run."""
+NO other flags must exit 0 and print ONE JSON line that carries the contract fields; with `--full` the line also carries
+the roofline block (HBM fraction and the vector-ALU bound), the CPU baseline and the other side measurements.  Round 2 lost
+its headline to a bench.py edit that was never run with the default arguments; these tests are those runs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -36,8 +37,39 @@ def _contract(d, steps, warmup):
     assert isinstance(d["config"].get("workload"), str) and "model" not in d["config"]
 
 
-def test_driver_command_default_flags():
-    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+SIDE_BLOCKS = ("roofline", "roofline_temporal", "cpu_baseline", "train_step", "channels_last", "warm_ms_per_step",
+               "eager_ms_per_step", "breakdown_ms")
+LEAVES = ("disp_teacher", "disp_student", "axisangle_m1", "translation_m1", "axisangle_p1", "translation_p1")
+
+
+def test_driver_command_default_flags(tmp_path):
+    """the plain command times the headline and nothing else; --dump-outputs writes what its last timed step returned, and
+    two runs with the same arguments return the same arrays"""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for out in dirs:
+        d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)])
+        _contract(d, 2, 1)
+        assert "--temporal --distil" in d["config"]["workload"] and d["config"]["width"] == 640 and d["config"]["global_batch"] == 12
+        assert abs(d["value"] - 12 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["batches_rotated"] == 6 and d["config"]["regime"].startswith("cold")
+        assert d["cold_ms_per_step"] == d["ms_per_step"] and d["cold_value"] == d["value"]
+        for k in SIDE_BLOCKS:
+            assert k not in d, k
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert "loss.loss.npy" in names and all("grad.%s.npy" % k in names for k in LEAVES), names
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert a.shape == b.shape and np.array_equal(a, b), (n, float(np.abs(a.astype(np.float64) - b).max()))
+    g = np.load(dirs[0] / "grad.disp_teacher.npy")
+    assert g.shape == (12, 1, 192, 640) and np.abs(g).max() > 0
+    assert np.load(dirs[0] / "loss.loss.npy").shape == ()
+
+
+def test_full_run_adds_the_side_measurements():
+    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full"])
     _contract(d, 2, 1)
     assert "--temporal --distil" in d["config"]["workload"] and d["config"]["width"] == 640 and d["config"]["global_batch"] == 12
     assert abs(d["value"] - 12 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
@@ -76,7 +108,8 @@ def test_driver_command_default_flags():
                                           (["--mode", "distil"], "--distil")],
                          ids=["dualrefine", "cityscapes_width", "distil"])
 def test_other_bench_modes_print_a_line(extra, expect):
-    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--train-steps", "0", "--loss-blc", "--rotate", "2"] + extra)
+    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--train-steps", "0", "--loss-blc", "--rotate", "2",
+                "--full"] + extra)
     _contract(d, 2, 1)
     if extra == ["--mode", "distil"]:  # the reference's own command adds --loss_blc (README.md:22): timed as its own block
         b = d["loss_blc"]
@@ -99,7 +132,7 @@ def test_two_ranks_over_gloo_print_the_multi_gpu_line():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rotate", "2",
-                        "--train-steps", "4"],
+                        "--train-steps", "4", "--full"],
                        env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][-1])
@@ -124,7 +157,7 @@ def test_two_ranks_over_gloo_print_the_multi_gpu_line():
 def test_value_train_makes_the_training_step_the_line():
     """`--value train`: the line's value / ms_per_step are the whole training step's, timed over exactly --steps steps; the
     loss-path measurement moves to the `loss_path` side block"""
-    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--value", "train", "--no-cpu-baseline", "--regime", "warm"])
+    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--value", "train", "--no-cpu-baseline", "--regime", "warm", "--full"])
     t = d["train_step"]
     assert "whole training step" in d["metric"] and d["value_is"].startswith("train_step")
     assert d["value"] == t["value"] and d["ms_per_step"] == t["ms_per_step"] and d["steps"] == 2 and t["steps"] == 2
