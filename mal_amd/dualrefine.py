@@ -81,11 +81,13 @@ class DrLossStepFn(Function):
         texels_from = cfg[7] if len(cfg) > 7 else None  # the workspace of the step's first call (texels + identity term)
         want_dec = len(cfg) > 8 and cfg[8]               # parity instrumentation (tests): decision planes per iteration
         pu = cfg[9] if len(cfg) > 9 else None            # the pose-update losses: {"noise": (B,1,H,W) N(0,1) or None}
+        if noises is not None and len(noises) != n:
+            raise L.MalError("DrLossStepFn: one noise map per iteration (%d), or None; got %d" % (n, len(noises)))
         req, p = ops._req, ops._p
         tens = [None if t is None else req(t, "leaf") for t in leaves]  # (None: a pose-update operand that IS an iteration's)
         cons = [req(t, "input") for t in (color0, color_m1, color_p1, K, inv_K)]
         cm = None if cmask is None else req(cmask, "consistency_mask")
-        nz = [None if t is None else req(t, "noise") for t in (noises or [None] * n)]
+        nz = [None if t is None else req(t, "noise") for t in (noises if noises is not None else [None] * n)]
         B, _, H, W = cons[0].shape
         dev = tens[0].device
         a = L.DrArgs()
@@ -386,6 +388,9 @@ class DualRefineLossPath:
                 philox = config.noise_seed
             else:
                 noises = [loss_utils.draw_noise((B, 1, H, W), target.device) for _ in units]  # one draw per visit (:586-587)
+        if noises is not None and len(noises) != len(units):
+            raise L.MalError("loss_step: `noises` holds one map per visited (scale, iteration), %d here %s; got %d"
+                             % (len(units), units, len(noises)))
         if pose_update and pose_noise is None and not opt.disable_automasking and philox is None:
             pose_noise = loss_utils.draw_noise((B, 1, H, W), target.device)
         losses, total, k = {}, None, 0
@@ -419,12 +424,13 @@ class DualRefineLossPath:
                     raise L.MalError("loss_step: pose_noise given while the other maps are drawn in the kernels (pass `noises` too)")
                 # upstream's default pairing re-uses the iterations' own tensors (the last disparity, the refined pose, frame
                 # +1's pose of iteration 0): their pose-update gradients then join the iteration's inside the assembly launch
+                # (j, not k: k is the running index into `noises`)
                 into = []
-                for k, own in enumerate((disps, disps, T_m1, T_p1)):
-                    hit = [i for i, t in enumerate(own) if t is pu_leaves[k]]
+                for j, own in enumerate((disps, disps, T_m1, T_p1)):
+                    hit = [i for i, t in enumerate(own) if t is pu_leaves[j]]
                     into.append(hit[0] if hit else None)
                     if hit:
-                        pu_leaves[k] = None
+                        pu_leaves[j] = None
                 pu = {"noise": None if opt.disable_automasking else pose_noise, "into": tuple(into)}
             cfg = (opt.min_depth, opt.max_depth, opt.disparity_smoothness / (2 ** scale), flags, n, philox, scale, first_ws,
                    bool(want_decisions), pu)

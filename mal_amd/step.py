@@ -419,6 +419,8 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
     aa = {f: mono_outputs[("axisangle", 0, f)] for f in (-1, 1)}
     tr = {f: mono_outputs[("translation", 0, f)] for f in (-1, 1)}
     fix = lambda t: t[:, 0] if t.dim() == 4 else t  # the pose decoder emits (B,2,1,3); frame 0 of it is used
+    if noise is not None and tuple(noise.shape) != (B, 1, H, W):
+        raise L.MalError("loss_step: the tie-break noise must be (B,1,H,W) = %s; got %s" % ((B, 1, H, W), tuple(noise.shape)))
     philox = None
     if noise is None:  # (loss_utils.compute_mono_losses adds the noise whatever --disable_automasking says, loss_utils.py:105-106)
         if config.noise_source == "philox":  # drawn inside the step's first kernel: no RNG launch, no host work
@@ -515,6 +517,8 @@ class MultiScaleLossFn(Function):
         hint = cfg[6] if len(cfg) > 6 else None  # --temporal: (image_synthesis, inputs, mono_outputs)
         want_dec = len(cfg) > 9 and cfg[9]         # parity instrumentation (tests): per-scale decision planes
         S = sclm + 1
+        if noises is not None and len(noises) != S:
+            raise L.MalError("MultiScaleLossFn: one noise map per scale (%d), or None; got %d" % (S, len(noises)))
         req, p = ops._req, ops._p
         tens = [req(t, "leaf") for t in leaves]
         cons = [req(t, "input") for t in (*colors, *colors_s, K, inv_K, cmask, keep)]
@@ -630,6 +634,8 @@ def loss_step_multiscale(opt, inputs, mono_outputs, outputs, noises=None, want_m
     from . import config, loss_utils
     sclm = int(getattr(opt, "sclm", 0))
     temporal = bool(getattr(opt, "temporal", False))
+    if noises is not None and len(noises) != sclm + 1:
+        raise L.MalError("loss_step_multiscale: `noises` holds one map per scale 0..%d; got %d" % (sclm, len(noises)))
     if temporal and image_synthesis is None:
         raise L.MalError("loss_step_multiscale with opt.temporal needs image_synthesis(inputs, outputs, scale) -> has_ins")
     unsupported = [k for k in ("distil", "v1_multiscale") if getattr(opt, k, False)]
