@@ -360,6 +360,27 @@ int mal_loss_step_abort(const mal_step_args* args);
  * after all (its producer is not one whose backward can be redirected); the side stream is joined back at once. */
 int mal_loss_step_tail_begin(const mal_step_args* args, void** stream);
 int mal_loss_step_tail_cancel(const mal_step_args* args);
+/* --distil with --scales 0..sclm (sclm 1..3) and the temporal hint: generate_images_pred (manydepth/trainer.py:1088-1165) warps
+ * the full-resolution sources once more per scale s > 0 with ("disp", s) upsampled (bilinear, align_corners=False) and calls
+ * the producer on each; the losses read scale 0 only, and has_ins is the LAST call's answer.  mal_loss_step_warp_scales
+ * enqueues those warps -- ONE forward-only launch for every hinted pass (teacher: MAL_STEP_TEMPORAL, student:
+ * MAL_STEP_MAIN_TEMPORAL) and scale -- on args->stream; call it right after mal_loss_step_warp on the same args / ws (it reads
+ * the camera block and texels of that call's first sweep), before the producers.  The producers' answers then go into
+ * scale 0's exchange (has_ins of the last call decides whether syn_* join the min); nothing of scales > 0 reaches
+ * mal_loss_step_fwd / _bwd, and their disparities receive no gradient.  MAL_EINVAL: sclm outside 1..3, no hinted pass, a NULL
+ * disparity or warp of a hinted pass, one of a warp2 pair NULL; MAL_ESHAPE: H or W not divisible by 2**sclm -- all before any
+ * device work. */
+enum { MAL_MS_MAX_SCALES = 4 };  /* scales 0..3 (mal_step_scales_args, mal_ms_args) */
+typedef struct mal_step_scales_args {
+  int sclm;                                           /* 1..3; index [s] = scale s, [0] unused */
+  const float *disp_teacher[MAL_MS_MAX_SCALES], *disp_student[MAL_MS_MAX_SCALES]; /* (B,1,H>>s,W>>s) */
+  float *warp_m1[MAL_MS_MAX_SCALES], *warp_p1[MAL_MS_MAX_SCALES];       /* out: ("color", f, s) of the teacher, (B,3,H,W)
+                                                                            planar, args->warp_sample_stride apart */
+  float *warp_s_m1[MAL_MS_MAX_SCALES], *warp_s_p1[MAL_MS_MAX_SCALES];   /* ... of the student */
+  float *warp2_m1[MAL_MS_MAX_SCALES], *warp2_p1[MAL_MS_MAX_SCALES];     /* nullable: contiguous (B,3,H,W) second copies */
+  float *warp2_s_m1[MAL_MS_MAX_SCALES], *warp2_s_p1[MAL_MS_MAX_SCALES];
+} mal_step_scales_args;
+int mal_loss_step_warp_scales(const mal_step_args* args, const mal_step_scales_args* scales);
 /* MAL_STEP_MAIN_TEMPORAL: call after mal_loss_step_warp (and after the teacher's producer, with MAL_STEP_TEMPORAL) and BEFORE the
  * student's producer reads warp_s_*: with both hints the student's forward pass runs on the library's side stream beside the
  * teacher's producer chain, and args->stream waits for it here (a no-op when the pass ran on args->stream itself). */
@@ -401,7 +422,6 @@ int mal_loss_step_bwd(const mal_step_args* args);
  * 2 marching launches + 2 smoothness sweeps per scale, one reduction), one backward (adjoint upsampling, gathered in a
  * fixed order: no atomics).  --v1_multiscale, --ensemble are not covered (MAL_EINVAL is not how they fail: the Python
  * mirror routes them through the operator-level API); --no_ssim: MAL_STEP_NO_SSIM; the temporal hint: MAL_STEP_TEMPORAL. */
-enum { MAL_MS_MAX_SCALES = 4 };
 typedef struct mal_ms_args {
   int B, H, W, sclm;                              /* scale s is (H >> s, W >> s); H, W divisible by 2**sclm */
   float min_depth, max_depth;
@@ -719,7 +739,8 @@ int mal_set_option(const char* name, int value);
  * (mal_profile_next_pass, mal_decisions_next_pass) are process-wide too (a step's backward runs on autograd's worker
  * thread, not on the arming one) and are taken with an atomic exchange: exactly one pass consumes an arm. */
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
-/* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item;
+/* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
+ * 4 mal_step_scales_args;
  * else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
 

@@ -87,6 +87,7 @@ SIGNATURES = {
     "mal_loss_step_fwd": (i32, [vp]),
     "mal_loss_step_bwd": (i32, [vp]),
     "mal_loss_step_warp": (i32, [vp]),
+    "mal_loss_step_warp_scales": (i32, [vp, vp]),
     "mal_loss_step_student_ready": (i32, [vp]),
     "mal_loss_step_abort": (i32, [vp]),
     "mal_loss_step_tail_begin": (i32, [vp, vp]),
@@ -140,6 +141,12 @@ class StepArgs(C.Structure):
                  ("g_syn_region_p1", vp), ("ens_disp", vp), ("g_ens_disp", vp)] +
                 [(n, vp) for n in ("warp_s_m1", "warp_s_p1", "syn_s_m1", "syn_s_p1", "g_syn_s_m1", "g_syn_s_p1", "g_warp_s_m1",
                                    "g_warp_s_p1", "syn_s_region", "g_syn_s_region_m1", "g_syn_s_region_p1")])
+
+
+class StepScalesArgs(C.Structure):
+    """mal_step_scales_args (include/mal_hip.h)."""
+    _fields_ = [("sclm", i32)] + [(n, vp * 4) for n in ("disp_teacher", "disp_student", "warp_m1", "warp_p1", "warp_s_m1", "warp_s_p1",
+                                                         "warp2_m1", "warp2_p1", "warp2_s_m1", "warp2_s_p1")]
 
 
 class MsArgs(C.Structure):
@@ -208,7 +215,7 @@ def load():
         fn.argtypes = args
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
-    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem)):
+    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

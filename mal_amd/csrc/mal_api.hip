@@ -24,6 +24,7 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 1: return sizeof(mal_ms_args);
     case 2: return sizeof(mal_dr_args);
     case 3: return sizeof(mal_dyn_item);
+    case 4: return sizeof(mal_step_scales_args);
     default: return 0;
   }
 }

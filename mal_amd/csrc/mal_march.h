@@ -242,6 +242,17 @@ MAL_DEV void upsample_pixels(const UpMaps& m, int k, int row, int x0, int H, int
   if (V == 4) *reinterpret_cast<float4*>(d) = make_float4(o[0], o[1], o[2], o[3]);
   else d[0] = o[0];
 }
+// The one-call step's extra scales (mal_loss_step_warp_scales): map k = one (pass, scale) pair -- its (B,1,h,w) disparity,
+// upsampled to (H,W) inside the kernel, warps both full-resolution sources; out[k][f]: planar (B,3,H,W) images `stride` floats
+// apart per sample, out2[k][f]: nullable contiguous second copies.  src: the step's texels; cam: its camera block.
+constexpr int kWarpScaleMaps = 2 * (MAL_MS_MAX_SCALES - 1);
+struct WarpScaleMaps {
+  int n;
+  const float* disp[kWarpScaleMaps]; int h[kWarpScaleMaps], w[kWarpScaleMaps];
+  float* out[kWarpScaleMaps][2]; float* out2[kWarpScaleMaps][2];
+};
+int warp_scales_launch(const WarpScaleMaps& m, const float* const src[2], const float* cam, int B, int H, int W,
+                       float min_depth, float max_depth, int stride, hipStream_t st);
 // workgroup e (64 threads) of an MsExtra: the noise maps' groups first (map e / noise_blocks; numbering of
 // tiebreak_noise_kernel: step number (counter ? *counter : step) * mult + map), then the upsampled maps' quads
 MAL_DEV void ms_extra_block(const MsExtra& p, int e, int tid) {

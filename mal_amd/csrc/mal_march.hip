@@ -1762,6 +1762,73 @@ int pack_identity_launch(const float* target, const float* src0, const float* sr
   return launch_status();
 }
 
+// The extra scales of the one-call step (mal_loss_step_warp_scales): per (map, sample, pixel) the scale's disparity upsampled
+// inline (upsample_pixels' arithmetic: bit-identical to mal_upsample_bilinear), then the scale-0 warp of both frames --
+// warp_issue / warp_finish, the camera block and texels the step's first sweep left -- and the planar images out.  Forward
+// only; one thread per pixel, a wave = 64 consecutive columns of one row (coalesced stores, neighbouring taps).
+struct WarpScalesParams {
+  WarpScaleMaps m;
+  const float* src[2]; const float* cam;
+  int B, H, W, stride;
+  float min_disp, range;
+};
+template <bool LEAN>
+__global__ __launch_bounds__(256) void warp_scales_kernel(WarpScalesParams p) {
+  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+  const int k = blockIdx.z / p.B, b = blockIdx.z - k * p.B;
+  const int H = p.H, W = p.W;
+  if (x >= W || y >= H) return;
+  const int h = p.m.h[k], w = p.m.w[k];
+  const Tap ty = tap_of(y, (float)h / (float)H, h), tx = tap_of(x, (float)w / (float)W, w);
+  const float* s0 = p.m.disp[k] + (size_t)b * h * w + (size_t)ty.i0 * w;
+  const float* s1 = p.m.disp[k] + (size_t)b * h * w + (size_t)ty.i1 * w;
+  const float dispv = bilinear_value(ty.l0, ty.l1, tx.l0, tx.l1, s0[tx.i0], s0[tx.i1], s1[tx.i0], s1[tx.i1]);
+  f2 P[12];
+  float ik[9];
+  load_cam((const cfloat*)(p.cam + (size_t)b * kCamFloats), P, ik);
+  WarpConsts wc = {};
+  wc.src[0] = p.src[0]; wc.src[1] = p.src[1]; wc.packed = 1; wc.W = W; wc.H = H; wc.convention = 0;
+  wc.min_disp = p.min_disp; wc.range = p.range; wc.eps = 1e-7f;
+  wc.rw = refined_rcp((float)(W - 1)); wc.rh = refined_rcp((float)(H - 1));  // the passes' grid normalisation (convention 0)
+  PendingWarp pw;
+  warp_issue<false, false, false, LEAN>(wc, P, ik, b, y, x, dispv, pw, []() {});
+  f2 c[3];
+  DerivRow d;
+  warp_finish<false, false>(pw, c, d);
+  const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+  float* const o0 = p.m.out[k][0] + (size_t)b * p.stride + pix;
+  float* const o1 = p.m.out[k][1] + (size_t)b * p.stride + pix;
+  o0[0] = c[0].x; o0[HW] = c[0].y; o0[2 * HW] = c[2].x;
+  o1[0] = c[1].x; o1[HW] = c[1].y; o1[2 * HW] = c[2].y;
+  if (p.m.out2[k][0]) {
+    float* const q0 = p.m.out2[k][0] + (size_t)b * 3 * HW + pix;
+    float* const q1 = p.m.out2[k][1] + (size_t)b * 3 * HW + pix;
+    q0[0] = c[0].x; q0[HW] = c[0].y; q0[2 * HW] = c[2].x;
+    q1[0] = c[1].x; q1[HW] = c[1].y; q1[2 * HW] = c[2].y;
+  }
+}
+
+int warp_scales_launch(const WarpScaleMaps& m, const float* const src[2], const float* cam, int B, int H, int W,
+                       float min_depth, float max_depth, int stride, hipStream_t st) {
+  if (m.n < 1 || m.n > kWarpScaleMaps || !src[0] || !src[1] || !cam) return MAL_EINVAL;
+  if ((long long)H * W >= (1ll << 24)) return MAL_ESHAPE;  // tap offsets use 24-bit multiplies
+  if ((long long)B * m.n > 65535) return MAL_ESHAPE;        // grid z
+  for (int k = 0; k < m.n; ++k) {
+    if (!m.disp[k] || !m.out[k][0] || !m.out[k][1] || (m.out2[k][0] == nullptr) != (m.out2[k][1] == nullptr)) return MAL_EINVAL;
+    if (m.h[k] < 1 || m.w[k] < 1 || m.h[k] > H || m.w[k] > W) return MAL_ESHAPE;
+  }
+  const MarchParams mp = march_params(B, H, W, min_depth, max_depth, 1e-7f, 0);
+  WarpScalesParams p;
+  p.m = m; p.src[0] = src[0]; p.src[1] = src[1]; p.cam = cam;
+  p.B = B; p.H = H; p.W = W; p.stride = stride > 0 ? stride : 3 * H * W;
+  p.min_disp = mp.min_disp; p.range = mp.range;
+  const dim3 grid((W + 63) / 64, (H + 3) / 4, B * m.n), block(64, 4);
+  // tap byte offsets in fp32 (LEAN) only where every one is below 2^24, as march_launch decides
+  if ((long long)H * W * (kTexel * 4) < (1ll << 24)) hipLaunchKernelGGL(warp_scales_kernel<true>, grid, block, 0, st, p);
+  else hipLaunchKernelGGL(warp_scales_kernel<false>, grid, block, 0, st, p);
+  return launch_status();
+}
+
 }  // namespace mal
 
 using namespace mal;

@@ -928,6 +928,41 @@ extern "C" int mal_loss_step_warp(const mal_step_args* a) {
   return MAL_OK;
 }
 
+// --distil with sclm > 0 and the temporal hint: the full-resolution warps of scales 1..sclm of every hinted pass, what the
+// producer is called on after scale 0's (upstream reads nothing else of them).  Forward only, one launch, after
+// mal_loss_step_warp on the same args / ws (the camera block and texels of its first sweep).
+extern "C" int mal_loss_step_warp_scales(const mal_step_args* a, const mal_step_scales_args* sc) {
+  if (!a || !sc) return MAL_EINVAL;
+  const int sclm = sc->sclm;
+  if (sclm < 1 || sclm >= MAL_MS_MAX_SCALES) return MAL_EINVAL;
+  int rc = check_shape(a->B, a->H, a->W);
+  if (rc) return rc;
+  if (a->H % (1 << sclm) || a->W % (1 << sclm)) return MAL_ESHAPE;
+  const bool temporal = a->flags & MAL_STEP_TEMPORAL, main_t = a->flags & MAL_STEP_MAIN_TEMPORAL;
+  if (!temporal && !main_t) return MAL_EINVAL;
+  WarpScaleMaps m = {};
+  for (int student = 0; student < 2; ++student) {
+    if (!(student ? main_t : temporal)) continue;
+    for (int s = 1; s <= sclm; ++s) {
+      const int k = m.n++;
+      m.disp[k] = student ? sc->disp_student[s] : sc->disp_teacher[s];
+      m.h[k] = a->H >> s; m.w[k] = a->W >> s;
+      m.out[k][0] = student ? sc->warp_s_m1[s] : sc->warp_m1[s];
+      m.out[k][1] = student ? sc->warp_s_p1[s] : sc->warp_p1[s];
+      m.out2[k][0] = student ? sc->warp2_s_m1[s] : sc->warp2_m1[s];
+      m.out2[k][1] = student ? sc->warp2_s_p1[s] : sc->warp2_p1[s];
+      if (!m.disp[k] || !m.out[k][0] || !m.out[k][1] || (m.out2[k][0] == nullptr) != (m.out2[k][1] == nullptr)) return MAL_EINVAL;
+    }
+  }
+  rc = step_check(a);
+  if (rc) return rc;
+  StepWs w = carve_step(a->ws, a->B, a->H, a->W);
+  use_texel_inputs(a, w);
+  const float* src[2] = {w.packed[1], w.packed[2]};
+  return warp_scales_launch(m, src, w.cam, a->B, a->H, a->W, a->min_depth, a->max_depth, a->warp_sample_stride,
+                            (hipStream_t)a->stream);
+}
+
 extern "C" int mal_loss_step_fwd(const mal_step_args* a) {
   int rc = step_check(a);
   if (rc) return rc;

@@ -318,6 +318,59 @@ class _Hint:
         return on_stream
 
 
+_SCALE_BUFS = {}
+
+
+def _scale_buffers(dev, B, H, W, student, s):
+    """the (B,2,3,H,W) warped pair and the two syn buffers of scale ``s`` > 0 of a pass, kept per (device, stream, shape,
+    workspace slot): rotating batches (``workspace_slot``) keep their own, a graph replay finds the captured ones"""
+    key = (dev.index, ops._stream(), B, H, W, _WS_SLOT, student, s)
+    bufs = _SCALE_BUFS.get(key)
+    if bufs is None:
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        bufs = _SCALE_BUFS[key] = (new((B, 2, 3, H, W)), new((B, 3, H, W)), new((B, 3, H, W)))
+    return bufs
+
+
+class _ScaleHint:
+    """Scale ``s`` > 0 of a hinted pass with --distil (mal_step_scales_args): generate_images_pred warps the full-resolution
+    sources with ("disp", s) upsampled and calls the producer on them (trainer.py:1088-1165), but no loss reads what it
+    leaves -- only its answer counts, and only the last scale's.  Forward only: the warped images carry no gradient and no
+    backward is ever run for them."""
+
+    def __init__(self, sa, student, s, B, H, W, dev):
+        self.student, self.scale = student, s
+        self.pair, pre0, pre1 = _scale_buffers(dev, B, H, W, student, s)
+        self.pre = (pre0, pre1)
+        self.warp = [self.pair[:, 0], self.pair[:, 1]]
+        tag = "_s" if student else ""
+        getattr(sa, "warp" + tag + "_m1")[s], getattr(sa, "warp" + tag + "_p1")[s] = (t.data_ptr() for t in self.warp)
+        self.has_ins, self.local = False, None
+
+    def produce(self, synth, inputs):
+        sc = self.scale
+        local = {("color", -1, sc): self.warp[0], ("color", 1, sc): self.warp[1], ("color_pair", sc): self.pair,
+                 ("syn_sparse_buffers", sc): self.pre}
+        with torch.no_grad():
+            self.has_ins = bool(synth(inputs, local, sc))
+        self.local = local
+
+    def expose(self, out, dense):
+        """("color", f, s) and, where the producer wrote them, ("syn", f, s), as _Hint.expose does for scale 0"""
+        sc, local = self.scale, self.local
+        out[("color", -1, sc)], out[("color", 1, sc)] = self.warp
+        if ("syn", -1, sc) not in local:
+            return
+        syn = [local[("syn", -1, sc)], local[("syn", 1, sc)]]
+        region = local.get(("syn_region", sc))
+        if local.get(("syn_sparse", sc)) and region is not None:
+            if dense:  # outside its regions a sparse producer's syn IS the warped image
+                inside = (region & 1).bool().unsqueeze(1)
+                out[("syn", -1, sc)], out[("syn", 1, sc)] = (torch.where(inside, t, w_) for t, w_ in zip(syn, self.warp))
+        else:
+            out[("syn", -1, sc)], out[("syn", 1, sc)] = (t.detach() for t in syn)
+
+
 class TemporalLossStepFn(Function):
     """The step with the temporal hint (``--temporal``, loss_utils.py:84-88; ``--main_temporal``, :152-155): three library
     calls around the producer ``synth(inputs, outputs, scale) -> has_ins`` (upstream: dyn_utils.image_synthesis), which
@@ -329,7 +382,10 @@ class TemporalLossStepFn(Function):
     before the chain rule through the warp.  ``which`` = (teacher hinted, student hinted); ``expose`` = (mono_outputs, outputs)."""
 
     @staticmethod
-    def forward(ctx, disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, synth, inputs, expose, which, ens_disp=None):
+    def forward(ctx, disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, synth, inputs, expose, which, ens_disp=None,
+                scales=None):
+        """``scales`` (--distil with sclm > 0): (sclm, teacher's ("disp", s) for s = 1..sclm, the student's) -- scale s of
+        every hinted pass is warped by mal_loss_step_warp_scales and handed to the producer after scale 0 (_ScaleHint)"""
         a, keep, maps = _build_args(disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, temporal=which[0],
                                     main_temporal=which[1], ens_disp=ens_disp)
         ctx.ens_index = 12
@@ -337,23 +393,42 @@ class TemporalLossStepFn(Function):
         dev = keep[0][0].device
         hints = [_Hint(a, student, B, H, W, dev) for student, on in ((False, which[0]), (True, which[1])) if on]
         a.warp_sample_stride = 6 * H * W
+        extra, sa, low = {h.student: [] for h in hints}, None, ()
+        if scales is not None:
+            sclm, low_t, low_s = scales
+            sa = L.StepScalesArgs()
+            sa.sclm = sclm
+            low = [ops._req(t.detach(), "disp") for t in (*low_t, *low_s)]
+            for s in range(1, sclm + 1):
+                sa.disp_teacher[s], sa.disp_student[s] = low[s - 1].data_ptr(), low[sclm + s - 1].data_ptr()
+            for h in hints:
+                extra[h.student] = [_ScaleHint(sa, h.student, s, B, H, W, dev) for s in range(1, sclm + 1)]
         lib = L.load()
         L.check(lib.mal_loss_step_warp(C.byref(a)), "mal_loss_step_warp")
         try:  # the producer raised, or left something unusable: join what mal_loss_step_warp forked before the buffers are reused
+            if sa is not None:
+                L.check(lib.mal_loss_step_warp_scales(C.byref(a), C.byref(sa)), "mal_loss_step_warp_scales")
             for h in hints:
                 if h.student:  # its warped images may have been written on the library's side stream
                     L.check(lib.mal_loss_step_student_ready(C.byref(a)), "mal_loss_step_student_ready")
-                h.produce(synth, inputs)
+                more = extra[h.student]
+                h.produce(synth, inputs, defer=bool(more))
+                if more:  # scales 1..sclm in upstream's order; the last call's answer stands for the pass (trainer.py:1162,1164)
+                    for e in more:
+                        e.produce(synth, inputs)
+                    h.finish(has_ins=more[-1].has_ins)
         except BaseException:
             lib.mal_loss_step_abort(C.byref(a))
             raise
         L.check(lib.mal_loss_step_fwd(C.byref(a)), "mal_loss_step_fwd")
         ctx.args, ctx.keep = a, keep
         ctx.ws_token = ops.claim_workspace(keep[2])
-        ctx.hints = hints  # the C struct holds their buffers' pointers
+        ctx.hints, ctx.scale_hints = hints, (low, extra)  # the C structs hold their buffers' pointers
         ctx.set_materialize_grads(False)
         for h in hints:
             h.expose(expose[1] if h.student else expose[0], cfg[5])
+            for e in extra[h.student]:
+                e.expose(expose[1] if h.student else expose[0], cfg[5])
         outs = [keep[4], keep[3]] + [maps[k] for k in MAP_NAMES if k in maps]
         ctx.mark_non_differentiable(*outs[1:])
         return tuple(outs)
@@ -362,7 +437,7 @@ class TemporalLossStepFn(Function):
     @once_differentiable
     def backward(ctx, g_total, *_):
         if g_total is None:
-            return (None,) * 13
+            return (None,) * 14
         # option "tail_overlap": the backward chain (producer's backward -> teacher's gradient sweep) on the library's side
         # stream, behind the fused sweep only -- beside the epilogue and the reduction the forward left on this stream
         lib, a = L.load(), ctx.args
@@ -377,7 +452,7 @@ class TemporalLossStepFn(Function):
             if side.value != a.stream and not (overlap and ok):  # nothing (or not everything) went there: join it back now
                 L.check(lib.mal_loss_step_tail_cancel(C.byref(a)), "mal_loss_step_tail_cancel")
         grads = _run_bwd(ctx, g_total)
-        return (*grads, None, None, None, None, None, None, ctx.g_ens)
+        return (*grads, None, None, None, None, None, None, ctx.g_ens, None)
 
 
 def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=None, noise=None, want_maps=True,
@@ -388,7 +463,12 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
     ``outputs[("disp", 0)]``, ``"consistency_mask"``, ``"augmentation_mask"``, ``"lowest_cost"``.
     With ``opt.temporal`` the producer ``image_synthesis(inputs, outputs, scale) -> has_ins`` is called between the
     library calls (``TemporalLossStepFn``); ``mono_outputs`` then receives ``("color", f, 0)``, ``("syn", f, 0)`` and
-    ``"has_ins"`` as the reference's generate_images_pred leaves them (trainer.py:1122-1125,1161-1165).  With
+    ``"has_ins"`` as the reference's generate_images_pred leaves them (trainer.py:1122-1125,1161-1165).
+    ``opt.sclm`` 1..3 (``--scales 0 .. sclm``): ``("disp", s)`` is read from both dicts for s <= sclm; the losses read
+    scale 0 only, so without a hint the result is the sclm = 0 step's and ``("disp", s > 0)`` gets no gradient; with one,
+    the producer is also called on each scale's full-resolution warp (forward only), after scale 0 in upstream's order,
+    ``("color", f, s)`` / ``("syn", f, s)`` are exposed, and the LAST call's answer decides whether scale 0's synthesised
+    images join the min (trainer.py:1088-1165).  With
     ``opt.main_temporal`` (trainer.py:1164, loss_utils.py:152-155) it is called for the student's pass as well -- after the
     teacher's, as upstream -- and ``outputs`` receives the same keys and ``"multi_has_ins"``.
     Writes ``outputs["consistency_mask"]`` (x matching mask, trainer.py:592-593) when ``want_maps``.
@@ -396,12 +476,25 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
     gradient passes (int32 (MAL_DEC_PLANES,B,H,W), include/mal_hip.h).
     Returns (losses dict, loss_list or None, maps dict)."""
     from . import config, loss_utils
-    if getattr(opt, "no_ssim", False) or not getattr(opt, "distil", True) or getattr(opt, "sclm", 0) != 0:
+    sclm = int(getattr(opt, "sclm", 0))
+    if getattr(opt, "no_ssim", False) or not getattr(opt, "distil", True):
         # (--no_ssim is read by Trainer.compute_reprojection_loss, trainer.py:1217, i.e. on the non-distil route only: the
         # distillation losses call loss_utils.compute_reprojection_loss, :46-55, which has no such branch -- and Trainer.ssim
         # does not exist then, trainer.py:318)
         raise L.MalError("loss_step covers the --distil [--temporal] [--main_temporal] [--learn_ens] [--no_ens [--dual_distil]] "
-                         "single-scale configuration; use MALLossPath.compute_batch_losses for no_ssim / non-distil runs")
+                         "configuration; use MALLossPath.compute_batch_losses for no_ssim / non-distil runs")
+    if sclm != 0:
+        # --scales 0..sclm: the losses read scale 0 only (loss_utils.py:57-200); the other scales only warp and call the
+        # temporal hint's producer (trainer.py:1088-1165), whose last answer decides
+        why = ("v1_multiscale with sclm > 0" if getattr(opt, "v1_multiscale", False) else
+               "sclm %d (0..%d)" % (sclm, L.MS_MAX_SCALES - 1) if not 0 < sclm < L.MS_MAX_SCALES else
+               "frame_ids %s (only [0, -1, 1])" % (list(opt.frame_ids),) if list(opt.frame_ids) != [0, -1, 1] else None)
+        H_, W_ = inputs[("color", 0, 0)].shape[-2:]
+        if why is None and (H_ % (1 << sclm) or W_ % (1 << sclm)):
+            why = "%dx%d not divisible by 2**sclm" % (H_, W_)
+        if why is not None:
+            raise L.MalError("loss_step with --distil covers sclm 1..%d with frames [0,-1,1] and sizes divisible by 2**sclm; "
+                             "%s: use MALLossPath.compute_batch_losses" % (L.MS_MAX_SCALES - 1, why))
     ens_disp = None
     if getattr(opt, "learn_ens", False) and not getattr(opt, "no_ens", False):
         # the learnt ensemble head's disparity (loss_utils.py:240-241, trainer.py:596-597): warped by the ensemble pass,
@@ -416,6 +509,16 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
     color0 = inputs[("color", 0, 0)]
     B, _, H, W = color0.shape
     dev = color0.device
+    scales = None
+    if sclm:
+        low = {}
+        for name, d in (("mono_outputs", mono_outputs), ("outputs", outputs)):
+            low[name] = [d[("disp", s)] for s in range(1, sclm + 1)]  # KeyError as upstream (trainer.py:1091)
+            for s, t in enumerate(low[name], 1):
+                if tuple(t.shape) != (B, 1, H >> s, W >> s) or t.dtype != torch.float32 or t.device != dev:
+                    raise L.MalError("loss_step: %s[('disp', %d)] must be a float32 (B,1,H>>%d,W>>%d) = %s tensor on %s; got %s %s"
+                                     % (name, s, s, s, (B, 1, H >> s, W >> s), dev, tuple(t.shape), t.dtype))
+        scales = (sclm, low["mono_outputs"], low["outputs"])
     aa = {f: mono_outputs[("axisangle", 0, f)] for f in (-1, 1)}
     tr = {f: mono_outputs[("translation", 0, f)] for f in (-1, 1)}
     fix = lambda t: t[:, 0] if t.dim() == 4 else t  # the pose decoder emits (B,2,1,3); frame 0 of it is used
@@ -444,7 +547,7 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
     if temporal or main_temporal:
         res = TemporalLossStepFn.apply(mono_outputs[("disp", 0)], outputs[("disp", 0)], fix(aa[-1]), fix(tr[-1]), fix(aa[1]),
                                        fix(tr[1]), consts, cfg, image_synthesis, inputs, (mono_outputs, outputs),
-                                       (temporal, main_temporal), ens_disp)
+                                       (temporal, main_temporal), ens_disp, scales)
     else:
         res = LossStepFn.apply(mono_outputs[("disp", 0)], outputs[("disp", 0)], fix(aa[-1]), fix(tr[-1]), fix(aa[1]),
                                fix(tr[1]), consts, cfg, ens_disp)
