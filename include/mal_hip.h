@@ -740,9 +740,55 @@ int mal_set_option(const char* name, int value);
  * thread, not on the arming one) and are taken with an atomic exchange: exactly one pass consumes an arm. */
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
 /* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
- * 4 mal_step_scales_args;
+ * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args;
  * else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
+
+/* ---- validation metrics: manydepth/trainer.py:836-1064 (Trainer.val) + evaluate_depth.py:35-53 (compute_errors) ----------
+ * The ground truth of a split is packed once (mal_amd/evaluate.py): per image a segment of `slots` packed points.  Sparse
+ * (LiDAR) segments hold the flat index y*gt_w+x of each valid point (mask and crop applied) and its value; dense segments
+ * (CityScapes windows) hold the rw-wide rectangle at (x0, y0) of the resized image row by row, with 0 where the mask is
+ * false.  `gt` is f64 when gt_f64, else fp32; med_gt is np.median of the image's valid ground truth (exact, in its dtype). */
+typedef struct mal_eval_seg {
+  int64_t off;     /* first packed slot of the image */
+  int slots;       /* packed slots (sparse: = n) */
+  int n;           /* valid points (>= 1) */
+  int gt_h, gt_w;  /* size the prediction is resized to (cv2.resize INTER_LINEAR, float32) */
+  int x0, y0, rw;  /* dense: the rectangle in the resized image; sparse: 0 */
+  int dense;
+  double med_gt;
+} mal_eval_seg;
+
+/* One batch of predictions: disp (B,1,H,W) are the network's sigmoid outputs for images first .. first+B-1.
+ * Per valid point: disp_to_depth(disp, min_depth_disp, max_depth_disp)[0] (as mal_disp_to_depth), the 4-tap resize,
+ * 1/x, x scale_factor; then per image an exact median, the ratio (median_scaling), the clamp to [clamp_min, clamp_max]
+ * and compute_errors.  img_out[i*8 + 0..7] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio (ratio = 1 without
+ * median scaling) for each image i of the batch; nothing else is written but `pred` (fp32 scratch: the batch's slots,
+ * seg[first+B-1].off + slots - seg[first].off of them).  resize_ulp moves each resized disparity by that many ulps
+ * (a measurement hook; 0 in use). */
+typedef struct mal_eval_args {
+  int n_images, first, B, H, W;
+  int gt_f64, median_scaling, resize_ulp;
+  double min_depth_disp, max_depth_disp;  /* as the Python floats upstream passes: 1/min_depth is formed in f64 */
+  float scale_factor, clamp_min, clamp_max;
+  const mal_eval_seg* seg;  /* device, [n_images] */
+  const int32_t* idx;       /* device, sparse flat indices (NULL if every segment is dense) */
+  const void* gt;           /* device, packed ground truth */
+  const float* disp;
+  float* pred;
+  double* img_out;          /* device, [n_images][8] */
+  void* stream;
+} mal_eval_args;
+
+int mal_eval_accumulate(const mal_eval_args* args);
+/* np.array(errors).mean(0): out7 = the mean of img_out[i*8 + 0..6] over the n_images images, in image order */
+int mal_eval_mean(const double* img_out, int n_images, double* out7, void* stream);
+/* compute_errors(gt, pred) on two device arrays of n values (each fp32 or f64, numpy's promotion: f64 arithmetic if
+ * either is f64, logs in each input's own dtype): out7 = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 as f64.
+ * Deterministic two-stage sum; ws >= mal_eval_errors_workspace_bytes(n). */
+size_t mal_eval_errors_workspace_bytes(size_t n);
+int mal_eval_errors(const void* gt, int gt_f64, const void* pred, int pred_f64, size_t n, double* out7, void* ws,
+                    size_t ws_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py): HIP events recorded immediately before / after the main
  * kernel of the NEXT mal_pass_fused call, on its stream (one-shot; cleared by that call). */

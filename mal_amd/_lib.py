@@ -114,6 +114,10 @@ SIGNATURES = {
     "mal_march_geometry": (i32, [i32, i32, i32, i32] + [C.POINTER(i32)] * 4),
     "mal_clock_probe": (i32, [vp, i32, vp]),
     "mal_decisions_next_pass": (i32, [vp]),
+    "mal_eval_accumulate": (i32, [vp]),
+    "mal_eval_mean": (i32, [vp, i32, vp, vp]),
+    "mal_eval_errors_workspace_bytes": (sz, [sz]),
+    "mal_eval_errors": (i32, [vp, i32, vp, i32, sz, vp, vp, sz, vp]),
 }
 
 class DynItem(C.Structure):
@@ -181,6 +185,20 @@ class DrArgs(C.Structure):
                 [(n, i32) for n in ("pu_disp_m1_into", "pu_disp_p1_into", "pu_T_m1_into", "pu_T_p1_into")])
 
 
+class EvalSeg(C.Structure):
+    """mal_eval_seg (include/mal_hip.h)."""
+    _fields_ = [("off", C.c_int64), ("slots", i32), ("n", i32), ("gt_h", i32), ("gt_w", i32), ("x0", i32), ("y0", i32),
+                ("rw", i32), ("dense", i32), ("med_gt", C.c_double)]
+
+
+class EvalArgs(C.Structure):
+    """mal_eval_args (include/mal_hip.h)."""
+    _fields_ = ([(n, i32) for n in ("n_images", "first", "B", "H", "W", "gt_f64", "median_scaling", "resize_ulp")] +
+                [(n, C.c_double) for n in ("min_depth_disp", "max_depth_disp")] +
+                [(n, f32) for n in ("scale_factor", "clamp_min", "clamp_max")] +
+                [(n, vp) for n in ("seg", "idx", "gt", "disp", "pred", "img_out", "stream")])
+
+
 DR_MAX_ITERS = 4
 DR_NO_AUTOMASK, DR_NO_MOTION_MASK, DR_NOISE_PHILOX, DR_AVG, DR_NO_SSIM, DR_POSE_UPDATE = 1, 2, 4, 8, 16, 32
 DR_POSE_NOISE_KEY = 0x706f73655f757064
@@ -215,7 +233,7 @@ def load():
         fn.argtypes = args
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
-    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs)):
+    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

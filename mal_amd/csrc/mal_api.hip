@@ -25,6 +25,8 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 2: return sizeof(mal_dr_args);
     case 3: return sizeof(mal_dyn_item);
     case 4: return sizeof(mal_step_scales_args);
+    case 5: return sizeof(mal_eval_seg);
+    case 6: return sizeof(mal_eval_args);
     default: return 0;
   }
 }

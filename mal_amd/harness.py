@@ -159,6 +159,36 @@ class TrainHarness:
         self.step_count += 1
         return losses
 
+    # ---- trainer.py:836-1064
+    def val(self, batches, evaluator, hard_test_mono=False):
+        """Trainer.val on the device: ``batches`` yields validation dicts (("color", 0, 0), ("color", -1, 0), ("K", 2),
+        ("inv_K", 2)) in the split's order; ``evaluator`` is a ``mal_amd.evaluate.DepthEvaluator`` of that split.  The
+        student's disparities go through disp_to_depth(., 1e-3, 80) (trainer.py:952), the teacher's through
+        disp_to_depth(., 1e-3, opt.max_depth) (:959), both fed to the evaluator batch by batch without a host round trip.
+        -> mean_errors, or (mean_errors, mean_errors_mono) when the teacher is not frozen (or ``hard_test_mono``)."""
+        opt = self.opt
+        mono_flag = not self.model.freeze_tp or hard_test_mono
+        lo, hi = self.tracker.compute()  # the tracker's current range, as process_batch uses it (trainer.py:937-947)
+        was_training = self.model.training
+        self.model.eval()
+        evaluator.reset()
+        first = 0
+        try:
+            with torch.no_grad():
+                for data in batches:
+                    data = {k: v.to(self.device) for k, v in data.items() if isinstance(v, torch.Tensor)}
+                    disp, disp_mono = self.model.val_forward(data, lo, hi, getattr(opt, "zero_cost_volume", False), mono_flag)
+                    evaluator.accumulate(disp, first, "student", 1e-3, 80,
+                                         not getattr(opt, "disable_median_scaling", False),
+                                         getattr(opt, "pred_depth_scale_factor", 1.0))
+                    if mono_flag:
+                        evaluator.accumulate(disp_mono, first, "mono", 1e-3, opt.max_depth, True, 1.0)
+                    first += disp.shape[0]
+        finally:
+            self.model.train(was_training)
+        mean = evaluator.result("student")[0]
+        return (mean, evaluator.result("mono")[0]) if mono_flag else mean
+
     def exchange_note(self):
         b = self.bucket
         return ("%d parameters (%.0f MB fp32) in one flat buffer, %d piece(s); last step: %d issued from inside the backward, "

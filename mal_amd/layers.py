@@ -13,7 +13,7 @@ from . import functional as Fn
 
 __all__ = ["disp_to_depth", "depth_to_disp", "transformation_from_parameters", "get_translation_matrix",
            "rot_from_axisangle", "BackprojectDepth", "Project3D", "Project3DDualRefine", "grid_sample",
-           "get_smooth_loss", "SSIM"]
+           "get_smooth_loss", "SSIM", "compute_depth_errors"]
 
 
 def disp_to_depth(disp, min_depth, max_depth):
@@ -123,3 +123,12 @@ class SSIM(nn.Module):
 
     def forward(self, x, y):
         return Fn.SSIMFn.apply(x, y)
+
+
+def compute_depth_errors(gt, pred):
+    """manydepth/layers.py:260-278 -> (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3), 0-dim tensors: the first four in
+    the inputs' promoted dtype, a1..a3 float32 (``.float().mean()``); computed by mal_eval_errors (fixed-order sums)."""
+    from .evaluate import _errors_f64
+    out, _ = _errors_f64(gt, pred)
+    dt = torch.promote_types(gt.dtype, pred.dtype)
+    return tuple(out[k].to(dt if k < 4 else torch.float32) for k in range(7))

@@ -326,6 +326,23 @@ class RepDepth(nn.Module):
                 inputs[("relative_pose", fi)] = pose * (~missing).to(pose.dtype)
         return outputs
 
+    def val_forward(self, data, min_depth_bin, max_depth_bin, zero_cost_volume=False, mono=True):
+        """the network half of Trainer.val for one batch (manydepth/trainer.py:862-963, need_pose_dec, frames 0 and -1):
+        the pose of frame -1 from ("color", f, 0) inverted, the lookup frame ("color", -1, 0), ("K", 2) / ("inv_K", 2), no
+        matching augmentation -> (student ("disp", 0), teacher ("disp", 0) or None).  Call under no_grad in eval mode."""
+        color0, color_m1 = data[("color", 0, 0)], data[("color", -1, 0)]
+        axisangle, translation = self._pose(color_m1, color0)
+        pose = transformation_from_parameters(axisangle[:, 0], translation[:, 0], invert=True)
+        lookup_frames = torch.stack([color_m1], 1)
+        relative_poses = torch.stack([pose], 1)
+        if zero_cost_volume:
+            relative_poses = relative_poses * 0
+        features, _, _ = self.encoder(color0, lookup_frames, relative_poses, data[("K", 2)], data[("inv_K", 2)],
+                                      min_depth_bin=min_depth_bin, max_depth_bin=max_depth_bin)
+        disp = self.depth(features)[("disp", 0)]
+        disp_mono = self.mono_depth(self.mono_encoder(color0))[("disp", 0)] if mono else None
+        return disp, disp_mono
+
     def forward(self, inputs, min_depth_bin, max_depth_bin):
         mono_outputs, outputs = {}, {}
         if not self.freeze_tp and not self.freeze_pose:
