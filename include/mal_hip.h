@@ -43,7 +43,10 @@ enum {
   MAL_ESHAPE = -2,    /* image smaller than 2x2 (reflection pad needs >= 2) or too large for int32 indexing */
   MAL_EWORKSPACE = -3,/* workspace too small: call mal_workspace_bytes */
   MAL_ELAUNCH = -4,   /* hipLaunchKernel / hipGetLastError failed */
-  MAL_ENODEVICE = -5  /* no HIP device */
+  MAL_ENODEVICE = -5, /* no HIP device */
+  MAL_ESTALE = -6     /* a later call of a one-call step (_fwd after _warp, _bwd) found options that change the task
+                         decomposition (march_rows, march_rows_fwd, pack_rows, march_halo1, device_cus) set differently
+                         from the step's first call */
 };
 
 /* flags for mal_pass_fused / mal_photo_* */
@@ -699,38 +702,58 @@ size_t mal_direct_align_bwd_workspace_bytes(int B, int h, int w); /* ws nullable
 int mal_direct_align_update_bwd(const float* H, const float* b, const float* poses, const float* g_new_poses,
                                 const float* g_update, int B, float* g_H, float* g_b, float* g_poses, void* stream);
 
-/* ---- library options:
- * "pass_impl"   formulation of the fused pass: 1 = register-marching (default); 0 / 2 = the LDS-tiled first
- *               versions (256 threads x 4 px, 512 threads x 2 px), kept for A/B;
- * "march_rows"  output rows per wavefront task of the marching kernels (0 = automatic, default);
- * "march_flip"  1 (default): odd row segments of the marching kernels walk bottom-up, so the two tasks sharing a
+/* ---- library options (mal_set_option / mal_get_option): exactly these names; value ranges in brackets, "0|1" switches take
+ * any int (nonzero = 1).  All of them are scheduling choices: none changes what a step computes.
+ * Task decomposition -- set before a step's first call and leave it until its _bwd (MAL_ESTALE otherwise):
+ * "march_rows"  [0..4096] output rows per wavefront task of the marching gradient passes; 0 (default) = automatic: the
+ *               smallest count >= 8 whose tasks fit one resident round of the device (CUs x 8 waves); values < 8 act as 8;
+ * "march_rows_fwd" [0..4096] the same for the forward-only passes; 0 (default) = as "march_rows";
+ * "pack_rows"   [8..4096] rows per task of the identity / packing sweep (default 10; the partials are sized for >= 8);
+ * "device_cus"  [0..65536] decompose as if the device had this many compute units (0, default: ask the device; a value
+ *               > 0 needs no device query, e.g. 32 = one MI355X CPX partition, 304 = MI300X);
+ * "march_halo1" 0|1 (default 1): the gradient passes of the whole-step lists warp ONE row beyond each end of a task's
+ *               segment and hand the boundary rows' missing terms over through scratch rows; 0: two rows, no hand-over (A/B);
+ * "march_flip"  0|1 (default 1): odd row segments of the marching kernels walk bottom-up, so the two tasks sharing a
  *               segment boundary reach it together and the halo rows are served by the L2; 0 = all top-down;
- * "costvol_impl" 1 (default): cost volume with planar features, lane = pixel; 0: channel-last, lane = channel;
- * "photo_impl"  mal_photo_fwd/bwd: 1 = marching kernels, two candidates per launch (default for SSIM + min);
- *               0 = one pixel per thread (ATen's summation order; always used for MAL_F_NO_SSIM / MAL_F_AVG);
- * "epi_bwd_planes" 2 (default): the feature-map cotangents of the N4 VJPs are accumulated per (sample, channel) plane in
- *               LDS when the planes fit, the lookup's with TWO channel planes per workgroup where 2 x the planes fit (round 4:
- *               coordinates, cotangent and tap set of a (pixel, hypothesis) pair serve both); 1: one plane per workgroup
- *               (round 3); 0: global float atomics everywhere (the first formulation, kept for A/B);
- * "step_overlap" 1 (default): with MAL_STEP_TEMPORAL the ensemble pass runs on a side stream beside the producer (forked
- *               after the warp pass, joined before the student pass; events, capturable); 0: in line; 2: beside the
- *               fused sweep (slower: kept for A/B);  "syn_rows": rows per task of the fused sweep given a region map;
- * "student_overlap" 1 (default): with MAL_STEP_TEMPORAL the student's marching pass (without its consistency / distillation
- *               epilogue, which becomes a pointwise launch after the join) is forked beside the producer behind the ensemble
- *               pass; 0: in line after the fused sweep, epilogue inside the pass (round 3, kept for A/B);
- * "march_halo1" 1 (default): the gradient passes of the whole-step lists warp ONE row beyond each end of a task's segment
- *               and hand the boundary rows' missing terms over through scratch rows; 0: two rows, no hand-over (A/B);
- * "march_lean"  1 (default): the teacher / student passes of the whole-step lists run the instantiations without the code
+ * "syn_rows"    [2..64] rows per task of the fused sweep given a region map (default 4; >= 8: the automatic decomposition);
+ * Formulations and overlap:
+ * "pass_impl"   [0..2] formulation of the fused pass: 1 = register-marching (default); 0 / 2 = the LDS-tiled first
+ *               versions (256 threads x 4 px, 512 threads x 2 px; -DMAL_EXPERIMENTS builds only);
+ * "march_lean"  0|1 (default 1): the teacher / student passes of the whole-step lists run the instantiations without the code
  *               of the optional operands they never pass (march_teacher_kernel, march_student_kernel); 0: generic (A/B);
- * "syn_queue"   1: the fused sweep over the synthesised pair takes its tasks from a classified dispatch order (slower,
- *               default 0);
- * "temporal_spec" 1: with MAL_STEP_TEMPORAL the pass in front of the producer already takes the teacher's gradient and the
- *               sweep behind the producer's backward only redoes the tasks near the region map (slower unless no sample
- *               has instances; default 0);
- * "march3"      1: the teacher's gradient pass as three cooperating wavefronts per strip, rows handed over through LDS
- *               (slower; default 0);
- * "epi_probe", "fwd_waves", "debug": kernel experiments / timing probes. */
+ * "costvol_impl" [0..1] 1 (default): cost volume with planar features, lane = pixel; 0: channel-last, lane = channel;
+ * "photo_impl"  [0..1] mal_photo_fwd/bwd: 1 = marching kernels, two candidates per launch (default for SSIM + min);
+ *               0 = one pixel per thread (ATen's summation order; always used for MAL_F_NO_SSIM / MAL_F_AVG);
+ * "epi_bwd_planes" [0..2] 2 (default): the feature-map cotangents of the N4 VJPs are accumulated per (sample, channel) plane
+ *               in LDS when the planes fit, the lookup's with TWO channel planes per workgroup where 2 x the planes fit;
+ *               1: one plane per workgroup; 0: global float atomics everywhere (the first formulation, kept for A/B);
+ * "dyn_small_blocks" 0|1 (default 1): the temporal-hint producer's extents kernel in small workgroups; 0: 1024 threads (A/B);
+ * "step_overlap" [0..2] 1 (default): with MAL_STEP_TEMPORAL the ensemble pass runs on a side stream beside the producer
+ *               (forked after the warp pass, joined before the student pass; events, capturable); 0: in line; 2: beside the
+ *               fused sweep (slower: kept for A/B);
+ * "student_overlap" 0|1 (default 1): with MAL_STEP_TEMPORAL the student's marching pass (without its consistency /
+ *               distillation epilogue, which becomes a pointwise launch after the join) is forked beside the producer behind
+ *               the ensemble pass; 0: in line after the fused sweep, epilogue inside the pass (kept for A/B);
+ * "side_order"  0|1 (default 0): 1 = of the forked passes the student's goes first, the ensemble pass behind it (slower);
+ * "side_priority" 0|1 (default 0): 1 = the side stream is created with the device's lowest priority (slower); read only when
+ *               a caller stream's side stream is first created;
+ * "tail_overlap" 0|1 (default 1): a --temporal step's backward chain runs on the side stream behind the fused sweep, beside
+ *               the epilogue and the reduction of the forward (mal_loss_step_tail_begin);
+ * "sweeps_batched" 0|1 (default 1): --temporal --main_temporal: both passes' fused sweeps as one launch; 0: two (A/B);
+ * "ms_fold"     0|1 (default 1): the four-scale step's noise maps and upsampling ride on its first sweep; 0: launches of
+ *               their own (A/B);
+ * "syn_queue"   0|1: the fused sweep takes its tasks from a classified dispatch order (slower, default 0;
+ *               -DMAL_EXPERIMENTS builds only);
+ * "temporal_spec" 0|1: with MAL_STEP_TEMPORAL the pass in front of the producer already takes the teacher's gradient and the
+ *               sweep behind the producer's backward only redoes the tasks near the region map (default 0;
+ *               -DMAL_EXPERIMENTS builds only);
+ * "march3"      0|1: the teacher's gradient pass as three cooperating wavefronts per strip, rows handed over through LDS
+ *               (slower; default 0; -DMAL_EXPERIMENTS builds only);
+ * Probes (timing / debugging experiments, results not meant to be used):
+ * "debug", "epi_probe" (any int; default 0). */
 int mal_set_option(const char* name, int value);
+int mal_get_option(const char* name, int* value); /* the current value of an option mal_set_option accepts; MAL_EINVAL for
+                                                   any other name */
 /* Options are PROCESS-WIDE switches for same-box A/B measurements, not per-call configuration: set them before the first
  * step and leave them; a second trainer in the process sees the same values.  Setting one is serialised by a mutex;
  * launches read them without further synchronisation.  The formulations that were measured slower (pass_impl 0 / 2,

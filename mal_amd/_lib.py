@@ -105,6 +105,7 @@ SIGNATURES = {
     "mal_upsample_bilinear": (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, vp]),
     "mal_upsample_bilinear_adjoint": (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, vp]),
     "mal_set_option": (i32, [C.c_char_p, i32]),
+    "mal_get_option": (i32, [C.c_char_p, C.POINTER(i32)]),
     "mal_build_has_experiments": (i32, []),
     "mal_struct_bytes": (sz, [i32]),
     "mal_event_create": (vp, []),

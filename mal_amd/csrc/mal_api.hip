@@ -14,6 +14,7 @@ extern "C" const char* mal_strerror(int code) {
     case MAL_EWORKSPACE: return "workspace too small (see mal_workspace_bytes)";
     case MAL_ELAUNCH: return "HIP kernel launch failed";
     case MAL_ENODEVICE: return "no HIP device";
+    case MAL_ESTALE: return "an option that sets the task decomposition changed between the calls of one step";
     default: return "unknown error";
   }
 }

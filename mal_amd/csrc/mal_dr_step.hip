@@ -362,6 +362,7 @@ extern "C" int mal_dr_loss_fwd(const mal_dr_args* a) {
   const bool automask = !(a->flags & MAL_DR_NO_AUTOMASK);
   const int pu = (a->flags & MAL_DR_POSE_UPDATE) ? 1 : 0;
   const bool philox = automask && (a->flags & MAL_DR_NOISE_PHILOX);
+  step_geom_record(a->ws, B, H, W);
   // identity term + texel packing (no noise here: every iteration adds its own).  Up to two iterations (the shipped
   // n_losses = 1): their edge-aware smoothness rides on this sweep, which holds the target rows anyway; more: one batched
   // smoothness sweep below
@@ -478,6 +479,8 @@ extern "C" int mal_dr_loss_bwd(const mal_dr_args* a) {
   if (rc) return rc;
   const int B = a->B, H = a->H, W = a->W, n = a->n_iters;
   DrWs w = carve_dr(a->ws, B, H, W, n);
+  rc = step_geom_check(a->ws, B, H, W);  // the boundary rows of _fwd are read with the decomposition it used
+  if (rc) return rc;
   DrAssemble p = {};
   for (int it = 0; it < n; ++it) {
     p.G_r[it] = w.G_r[it]; p.G_c[it] = w.G_c[it]; p.gn[it] = w.gn[it]; p.bnd[it] = g_march_halo1 ? w.bnd[it] : nullptr;

@@ -105,6 +105,10 @@ MarchParams march_params(int B, int H, int W, float min_depth, float max_depth, 
 int march_launch(MarchParams& p, int flags, hipStream_t st);
 // the decomposition march_launch picks for (B,H,W) and `flags` on the current device
 void march_geometry(int B, int H, int W, int flags, int* strips, int* segs, int* rows);
+// the one-call steps: the first call of a step records the decomposition it uses for workspace `ws`; the later calls check
+// that the options still give the same one (MAL_ESTALE otherwise)
+void step_geom_record(const void* ws, int B, int H, int W);
+int step_geom_check(const void* ws, int B, int H, int W);
 // floats of a boundary scratch buffer (MarchParams::bnd) that fits every decomposition of (B,H,W)
 inline size_t march_bnd_floats(int B, int H, int W) { return (size_t)B * ((size_t)H / 8 + 1) * 2 * (size_t)W; }
 // what the boundary scratch rows add to pixel (b, y, x) of the gradient map (0 away from segment boundaries); y, rows,

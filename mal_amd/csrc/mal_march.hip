@@ -33,6 +33,7 @@
 #include "mal_device.h"
 #include "mal_pairs.h"
 #include <mutex>
+#include <unordered_map>
 
 namespace mal {
 
@@ -1540,6 +1541,7 @@ opt_t g_march_flip{1};  // odd segments bottom-up (mal_set_option("march_flip", 
 opt_t g_march_rows{0};  // output rows per wave task; 0 = pick so that one round of tasks fills the chip
 opt_t g_pack_rows{10};  // rows per task of the identity / packing sweep: 20 segments x 11 strips x 12 samples = 2640 tasks <= 3072 (three waves per SIMD); same-box steps, round 3: 10: 0.2010 / 0.3270 ms (--distil / headline), 9: 0.2019 / 0.3290, 11: 0.2043 / 0.3291, 12: 0.329 (headline)
 opt_t g_march_rows_fwd{0};  // the same for the forward-only passes (<= 168 VGPRs: three waves per SIMD); 0 = automatic
+opt_t g_device_cus{0};  // option "device_cus": decompose as if the device had this many CUs (0 = ask the device)
 opt_t g_debug{0};
 std::atomic<unsigned*> g_dec_next{nullptr};  // mal_decisions_next_pass (one-shot, taken with an atomic exchange): decision planes for the next instrumentable gradient pass
 extern opt_t g_photo_impl;  // mal_photo_march.hip
@@ -1580,13 +1582,18 @@ static void march_decompose(MarchParams& p, int flags) {
     // waves per SIMD (<= 256 VGPRs): the shortest makespan is the smallest `rows` whose task count still
     // fits in ONE resident round (CUs x 4 SIMDs x 2).  Measured on MI355X at B=12 192x640: rows 13
     // (1980 tasks <= 2048) 124 us vs rows 16 135 us vs rows 12 (2112 tasks, two rounds) 164 us.
-    static int slots = 0;
-    if (slots == 0) {
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      (void)hipGetLastError();
-      if (cus <= 0) cus = 256;
-      slots = cus * 8;
+    // (option "device_cus" > 0 stands in for the queried count, without a device query)
+    static int queried = 0;
+    int slots = g_device_cus * 8;
+    if (slots <= 0) {
+      if (queried == 0) {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        (void)hipGetLastError();
+        if (cus <= 0) cus = 256;
+        queried = cus * 8;
+      }
+      slots = queried;
     }
     rows = 8;
     while (rows < p.H && (long long)p.B * p.strips * ((p.H + rows - 1) / rows) > slots) ++rows;
@@ -1829,6 +1836,40 @@ int warp_scales_launch(const WarpScaleMaps& m, const float* const src[2], const 
   return launch_status();
 }
 
+// The one-call steps leave per-task partials, boundary scratch rows and per-sample task counts in their workspace for the
+// step's later calls (_fwd after _warp, _bwd after _fwd), and each call derives the decomposition from the options again.
+// What the first call used is kept per workspace; a later call that would use another one is refused (MAL_ESTALE).
+struct StepGeom {
+  int rows_grad, rows_fwd, pack_rows, halo1;
+  bool operator==(const StepGeom& o) const {
+    return rows_grad == o.rows_grad && rows_fwd == o.rows_fwd && pack_rows == o.pack_rows && halo1 == o.halo1;
+  }
+};
+static StepGeom step_geom_now(int B, int H, int W) {
+  StepGeom g = {};
+  march_geometry(B, H, W, MAL_F_GRAD, nullptr, nullptr, &g.rows_grad);
+  march_geometry(B, H, W, 0, nullptr, nullptr, &g.rows_fwd);
+  g.pack_rows = g_pack_rows;
+  g.halo1 = g_march_halo1;
+  return g;
+}
+static std::mutex g_geom_mutex;
+static std::unordered_map<const void*, StepGeom> g_geom;  // workspace -> the decomposition its step's first call used
+
+void step_geom_record(const void* ws, int B, int H, int W) {
+  const StepGeom g = step_geom_now(B, H, W);
+  std::lock_guard<std::mutex> lock(g_geom_mutex);
+  if (g_geom.size() >= 4096 && !g_geom.count(ws)) g_geom.clear();  // (bounded: a forgotten workspace only loses its check)
+  g_geom[ws] = g;
+}
+
+int step_geom_check(const void* ws, int B, int H, int W) {
+  const StepGeom g = step_geom_now(B, H, W);
+  std::lock_guard<std::mutex> lock(g_geom_mutex);
+  auto it = g_geom.find(ws);
+  return it == g_geom.end() || it->second == g ? MAL_OK : MAL_ESTALE;
+}
+
 }  // namespace mal
 
 using namespace mal;
@@ -1890,9 +1931,29 @@ extern "C" int mal_set_option(const char* name, int value) {
   if (eq("epi_bwd_planes")) { if (value < 0 || value > 2) return MAL_EINVAL; g_epi_bwd_planes = value; return MAL_OK; }
   if (eq("epi_probe")) { g_epi_probe = value; return MAL_OK; }
   if (eq("march_flip")) { g_march_flip = value != 0; return MAL_OK; }
-  if (eq("pack_rows")) { if (value < 4 || value > 4096) return MAL_EINVAL; g_pack_rows = value; return MAL_OK; }
+  if (eq("pack_rows")) { if (value < 8 || value > 4096) return MAL_EINVAL; g_pack_rows = value; return MAL_OK; }  // >= 8: the partials are sized for 8-row tasks (ws_blocks)
   if (eq("march_rows_fwd")) { if (value < 0 || value > 4096) return MAL_EINVAL; g_march_rows_fwd = value; return MAL_OK; }
   if (eq("march_rows")) { if (value < 0 || value > 4096) return MAL_EINVAL; g_march_rows = value; return MAL_OK; }
+  if (eq("device_cus")) { if (value < 0 || value > 65536) return MAL_EINVAL; g_device_cus = value; return MAL_OK; }
+  return MAL_EINVAL;
+}
+
+extern "C" int mal_get_option(const char* name, int* value) {
+  if (!name || !value) return MAL_EINVAL;
+  static const struct { const char* name; const opt_t* v; } kOptions[] = {
+      {"pass_impl", &g_pass_impl}, {"debug", &g_debug}, {"photo_impl", &g_photo_impl}, {"costvol_impl", &g_costvol_impl},
+      {"step_overlap", &g_step_overlap}, {"march_halo1", &g_march_halo1}, {"student_overlap", &g_student_overlap},
+      {"ms_fold", &g_ms_fold}, {"sweeps_batched", &g_sweeps_batched}, {"tail_overlap", &g_tail_overlap},
+      {"dyn_small_blocks", &g_dyn_small_blocks}, {"side_order", &g_side_order}, {"side_priority", &g_side_priority},
+      {"temporal_spec", &g_temporal_spec}, {"march3", &g_march3}, {"march_lean", &g_march_lean}, {"syn_queue", &g_syn_queue},
+      {"syn_rows", &g_syn_rows}, {"epi_bwd_planes", &g_epi_bwd_planes}, {"epi_probe", &g_epi_probe},
+      {"march_flip", &g_march_flip}, {"pack_rows", &g_pack_rows}, {"march_rows_fwd", &g_march_rows_fwd},
+      {"march_rows", &g_march_rows}, {"device_cus", &g_device_cus}};
+  for (const auto& o : kOptions) {
+    const char *a = name, *s = o.name;
+    while (*a && *a == *s) { ++a; ++s; }
+    if (*a == *s) { *value = o.v->load(); return MAL_OK; }
+  }
   return MAL_EINVAL;
 }
 

@@ -892,6 +892,7 @@ extern "C" int mal_loss_step_warp(const mal_step_args* a) {
   hipStream_t st = (hipStream_t)a->stream;
   rc = join_side(st);  // a previous step that was abandoned after its fork (no _fwd, no _abort)
   if (rc) return rc;
+  step_geom_record(a->ws, a->B, a->H, a->W);
   int per_sample_p = 1;
   rc = first_sweep(a, w, st, &per_sample_p);
   if (rc) return rc;
@@ -975,6 +976,8 @@ extern "C" int mal_loss_step_fwd(const mal_step_args* a) {
   float* mono_reproj = a->mono_reproj ? a->mono_reproj : w.mono_reproj;
   float* ens_reproj = no_ens ? nullptr : (a->ens_reproj ? a->ens_reproj : w.ens_reproj);
   float* multi_reproj = a->multi_reproj;  // only written when the caller wants the map
+  if (!hinted) step_geom_record(a->ws, B, H, W);
+  else if (step_geom_check(a->ws, B, H, W)) { (void)join_side(st); return MAL_ESTALE; }  // options changed after _warp
 
   int per_sample_p = 1, per_sample_ph = 0;
   int per_sample = 1, per_sample_t = 0;
@@ -1124,6 +1127,8 @@ extern "C" int mal_loss_step_bwd(const mal_step_args* a) {
     SideStream* ss = side_stream(st);
     if (ss && ss->tail_pending) tail = ss;
   }
+  rc = step_geom_check(a->ws, B, H, W);  // the boundary rows, partials and task counts of _fwd need the decomposition it used
+  if (rc) { if (tail) (void)join_tail(tail, st); return rc; }
   if (a->flags & MAL_STEP_TEMPORAL) {
     // the teacher's gradient sweep, with the decisions of the four-way min taken from _fwd and the gradient that
     // reaches the warped images through syn added before the chain rule through the warp

@@ -746,6 +746,7 @@ extern "C" int mal_loss_multiscale_warp(const mal_ms_args* a) {
   int per_sm[kMsS], forked = 0;
   rc = side_wait((hipStream_t)a->stream, false);  // a previous step that was abandoned after its fork
   if (rc) return rc;
+  step_geom_record(a->ws, a->B, a->H, a->W);
   return ms_front(a, w, (hipStream_t)a->stream, true, per_sm, &forked);
 }
 
@@ -763,10 +764,12 @@ extern "C" int mal_loss_multiscale_fwd(const mal_ms_args* a) {
   const bool temporal = (a->flags & MAL_STEP_TEMPORAL) != 0;
   int per_sm[kMsS] = {};
   if (!temporal) {
+    step_geom_record(a->ws, a->B, a->H, a->W);
     int forked = 0;
     rc = ms_front(a, w, st, false, per_sm, &forked);
     if (rc) return rc;
   } else {
+    if (step_geom_check(a->ws, a->B, a->H, a->W)) { (void)side_wait(st, false); return MAL_ESTALE; }  // options changed after _warp
     for (int s = 0; s <= a->sclm; ++s) per_sm[s] = ms_smooth_tasks(a->H, a->W, s);
   }
   return ms_back(a, w, st, temporal, per_sm);
@@ -777,6 +780,8 @@ extern "C" int mal_loss_multiscale_bwd(const mal_ms_args* a) {
   if (rc) return rc;
   const int B = a->B, H = a->H, W = a->W, S = a->sclm + 1;
   MsWs w = carve_ms(a->ws, B, H, W, a->sclm);
+  rc = step_geom_check(a->ws, B, H, W);  // the boundary rows and partials of _fwd are read with the decomposition it used
+  if (rc) return rc;
   if (a->flags & MAL_STEP_TEMPORAL) {
     // the teacher's gradient sweep per scale, with the four-way decisions of _fwd and what reaches the warped images through
     // syn added before the chain rule through the warp; then the boundary rows and the pose partials it left
