@@ -13,11 +13,11 @@ from . import ops
 
 
 def _run(current_feats, lookup_feats, relative_poses, K, invK, depth_bins, set_missing_to_max, want):
+    B, C, h, w = current_feats.shape
+    if lookup_feats.dim() != 5 or lookup_feats.shape[0] != B or tuple(lookup_feats.shape[2:]) != (C, h, w):
+        raise L.MalError("lookup_feats must be (B,F,C,h,w) matching current_feats (B,C,h,w)")
     cur = ops._req(current_feats.detach(), "current_feats")
     look = ops._req(lookup_feats.detach(), "lookup_feats")
-    B, C, h, w = cur.shape
-    if look.dim() != 5 or look.shape[0] != B or tuple(look.shape[2:]) != (C, h, w):
-        raise L.MalError("lookup_feats must be (B,F,C,h,w) matching current_feats (B,C,h,w)")
     F_ = look.shape[1]
     dev = cur.device
     bins = torch.as_tensor(depth_bins, dtype=torch.float32).to(dev).contiguous().reshape(-1)

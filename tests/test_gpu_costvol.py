@@ -8,54 +8,16 @@ import numpy as np
 import pytest
 import torch
 
+from tests.costvol_checks import check
 from tests.test_costvol_oracle import CASES, load
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="session", autouse=True)
 def _built():
     from mal_amd import build
     build.build(verbose=False)
-
-
-def ambiguous(poses, K, invK, bins, B, h, w, tol=2e-4):
-    """(B,D,h,w) bool: the sampling position of (pixel, bin) in ANY frame lies within tol px of 2, w-2, h-2"""
-    from oracle import mal_oracle as O
-    D = bins.numel()
-    amb = torch.zeros(B, D, h, w, dtype=torch.bool)
-    depth = bins.view(D, 1, 1, 1).expand(D, 1, h, w).contiguous().double()
-    for b in range(B):
-        world = O.backproject_depth(depth, invK[b:b + 1].double().expand(D, 4, 4))
-        for f in range(poses.shape[1]):
-            pix = O.project_3d(world, K[b:b + 1].double().expand(D, 4, 4), poses[b:b + 1, f].double().expand(D, 4, 4), h, w)
-            x, y = (pix[..., 0] / 2 + 0.5) * (w - 1), (pix[..., 1] / 2 + 0.5) * (h - 1)
-            near = lambda v, t: (v - t).abs() <= tol
-            amb[b] |= near(x, 2.0) | near(x, w - 2.0) | near(y, 2.0) | near(y, h - 2.0)
-    return amb
-
-
-def check(cur, look, poses, K, invK, bins, ref):
-    from mal_amd import costvol
-    B, _, h, w = cur.shape
-    d = lambda t: t.to(DEV)
-    cv, miss = costvol.match_features(d(cur), d(look), d(poses), d(K), d(invK), bins, True)
-    masked, low, conf = costvol.cost_volume_outputs(d(cur), d(look), d(poses), d(K), d(invK), bins, True)
-    amb = ambiguous(poses, K, invK, bins, B, h, w)
-    amb_px = amb.any(1)                       # a flipped bin changes the pixel's max / confidence / argmin
-    ok = ~amb_px.unsqueeze(1).expand_as(amb)
-    r_cv, r_miss, r_masked, r_low, r_conf = ref
-    assert amb_px.float().mean() <= 0.02
-    assert (cv.cpu() - r_cv)[ok].abs().max() <= 1e-4 * max(1.0, float(r_cv.abs().max()))
-    assert torch.equal(miss.cpu()[ok], r_miss[ok])
-    assert (masked.cpu() - r_masked)[ok].abs().max() <= 1e-4 * max(1.0, float(r_cv.abs().max()))
-    assert torch.equal(conf.cpu()[~amb_px], r_conf[~amb_px])
-    # lowest_cost: the argmin may differ where two bins tie to 1e-5; compare the cost AT the chosen bin
-    pick = lambda vol, lowc: torch.gather(torch.where(vol == 0, torch.full_like(vol, 100.0), vol), 1,
-                                          (1 / lowc).unsqueeze(1).sub(bins.view(1, -1, 1, 1)).abs().argmin(1, keepdim=True))[:, 0]
-    a, bq = pick(r_cv, low.cpu()), pick(r_cv, r_low)
-    assert ((a - bq).abs() <= 2e-4 * bq.abs().clamp(min=1.0))[~amb_px].all()
 
 
 @pytest.mark.parametrize("impl", [1, 0], ids=["lane_pixel", "lane_channel"])

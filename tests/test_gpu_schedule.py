@@ -59,7 +59,7 @@ EXCLUDED = {
     "march_lean": "held bit for bit against the generic instantiations in tests/test_gpu_step.py",
     "tail_overlap": "held against the serial backward, eager and graph, in tests/test_gpu_step.py",
     "photo_impl": "a different summation order by design (ATen's); both held against the oracle in tests/test_gpu_layers.py",
-    "costvol_impl": "both formulations held in tests/test_gpu_costvol.py",
+    "costvol_impl": "both formulations held in tests/test_gpu_costvol.py and tests/test_gpu_costvol_sweep.py",
     "dyn_small_blocks": "held in tests/test_gpu_dyn.py",
 }
 
