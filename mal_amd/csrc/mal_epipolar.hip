@@ -975,6 +975,11 @@ __global__ __launch_bounds__(kPlaneThreads) void epi_align_bwd_planes_kernel(Epi
 
 // x = A^-1 rhs as PoseUpdate.direct_align does it (utils.py:357-368): Cholesky, else LU with partial pivoting, else failure.
 // `chol` says which succeeded.  Constant loop bounds, fully unrolled: the 6x6 arrays stay in registers.
+// The fall-back is decided per SAMPLE (a thread owns one): upstream decides per BATCH -- one sample that is not positive
+// definite sends every sample of the batch through linalg.solve, and a failure returns the whole batch's poses twice
+// (utils.py:364-374).  Here a bad sample changes its own row only, and a failed row's update is zero.  Where every sample
+// takes the same branch the two agree; the CPU checker's direct_align_per_sample restates this, and
+// tests/test_gpu_epipolar_sweep.py::test_solver_branches_in_one_batch holds all three outcomes side by side.
 MAL_DEV bool solve6(const float (&A)[6][6], const float (&rhs)[6], float (&x)[6], bool* chol) {
   float Lm[6][6];
   bool ok = true;

@@ -46,7 +46,7 @@ def depth2epipolarcoords(poses, depths, K, delta, r=8, num_levels=3, ratio=8):
     -> (coords (B,2,L,2r+1,h,w), max_dx (B,1,h,w), depths (B,1,L*(2r+1),h,w)).
     ``delta``: the module's learnable scalar (softplus'd here as upstream)."""
     bsz, _, ht, wd = depths.shape
-    dx = torch.linspace(-r, r, 2 * r + 1)[None, None, :, None, None]
+    dx = torch.linspace(-r, r, 2 * r + 1, dtype=depths.dtype)[None, None, :, None, None]
     depths = depths[:, None]
     dd = F.softplus(delta)
     gap = dd * depths / ratio / r
@@ -85,7 +85,8 @@ def coord_sample(fmap1, f2_pyramid, coords, num_levels=1, num_head=1):
         f2 = F.grid_sample(f2_pyramid[i], grid, align_corners=False).view(batch, -1, h1, w1, d1)
         corr = torch.abs(f1 - f2).view(batch, num_head, -1, h1, w1, d1).mean(2)
         outs.append(corr.permute(0, 2, 3, 1, 4).reshape(batch, h1, w1, -1))
-    return torch.cat(outs, dim=-1).permute(0, 3, 1, 2).contiguous().float()
+    out = torch.cat(outs, dim=-1).permute(0, 3, 1, 2).contiguous()
+    return out if out.dtype == torch.float64 else out.float()
 
 
 def depthbins2coords(poses, depths, K, min_depth, max_depth, num_depth_bins=96, bins_range=None):
@@ -120,8 +121,8 @@ def depth2gradcoords(poses, depths, K):
     X0 = iproj(depths[:, None], K)
     X1 = poses.type(X0.dtype) @ X0.reshape(bsz, 4, -1)
     c1 = proj(X1, K).reshape(bsz, 2, 1, 1, ht, wd)
-    p_dx = torch.tensor([1., 0.]).reshape(1, 2, 1, 1, 1, 1)
-    p_dy = torch.tensor([0., 1.]).reshape(1, 2, 1, 1, 1, 1)
+    p_dx = torch.tensor([1., 0.], dtype=c1.dtype).reshape(1, 2, 1, 1, 1, 1)
+    p_dy = torch.tensor([0., 1.], dtype=c1.dtype).reshape(1, 2, 1, 1, 1, 1)
     return torch.cat([c1, c1 + torch.cat([p_dx, -p_dx, p_dy, -p_dy], 3)], 3), X1
 
 
@@ -130,18 +131,18 @@ def se3_exp(vec):
     rho, phi = vec[:, :3], vec[:, 3:]
     theta = torch.norm(phi, 2, 1, keepdim=True)
     a = phi / theta
-    a_skew = torch.zeros((vec.shape[0], 3, 3))
+    a_skew = torch.zeros((vec.shape[0], 3, 3), dtype=vec.dtype)
     a_skew[:, 0, 1] = -a[:, 2, 0]
     a_skew[:, 0, 2] = a[:, 1, 0]
     a_skew[:, 1, 0] = a[:, 2, 0]
     a_skew[:, 1, 2] = -a[:, 0, 0]
     a_skew[:, 2, 0] = -a[:, 1, 0]
     a_skew[:, 2, 1] = a[:, 0, 0]
-    eye = torch.eye(3).unsqueeze(0)
+    eye = torch.eye(3, dtype=vec.dtype).unsqueeze(0)
     aat = torch.bmm(a, a.permute(0, 2, 1))
     R = torch.cos(theta) * eye + (1 - torch.cos(theta)) * aat + torch.sin(theta) * a_skew
     J = (torch.sin(theta) / theta) * eye + (1 - (torch.sin(theta) / theta)) * aat + (1 - torch.cos(theta)) / theta * a_skew
-    T = torch.eye(4).unsqueeze(0).repeat(vec.shape[0], 1, 1)
+    T = torch.eye(4, dtype=vec.dtype).unsqueeze(0).repeat(vec.shape[0], 1, 1)
     T[:, :3, :3] = R
     T[:, :3, -1:] = torch.bmm(J, rho.type(J.dtype))
     return T
@@ -169,7 +170,7 @@ def robust_weights(res, p2, height, width):
     pts, pad = p2[:, :, 0, 0], 2
     hi = torch.tensor([width - pad - 1, height - pad - 1]).to(pts).reshape(1, 2, 1, 1)
     valid = torch.all((pts >= pad) & (pts <= hi), 1, keepdim=True)
-    return w_loss * valid.float()
+    return w_loss * valid.to(w_loss.dtype)
 
 
 def normal_equations(src_feat, tgt_feat, src_w, tgt_w, K, p2, P2, weight=None, robust=False):
@@ -180,7 +181,7 @@ def normal_equations(src_feat, tgt_feat, src_w, tgt_w, K, p2, P2, weight=None, r
     fx, fy = K[:, 0, 0].reshape(-1, 1), K[:, 1, 1].reshape(-1, 1)
     fxz, fyz = fx / Z, fy / Z
     fxxz2, fyyz2 = fxz * X / Z, fyz * Y / Z
-    zeros = torch.zeros(fxxz2.shape)
+    zeros = torch.zeros_like(fxxz2)
     J_pixel_xi = torch.stack((torch.stack((fxz, zeros, -fxxz2, -fxxz2 * Y, fx + fxxz2 * X, -fxz * Y), 1),
                               torch.stack((zeros, fyz, -fyyz2, -fy - fyyz2 * Y, fyyz2 * X, fyz * X), 1)), 1)
     J_pixel_xi = J_pixel_xi.permute(0, 3, 1, 2)
@@ -204,3 +205,58 @@ def direct_align(poses, src_feat, tgt_feat, src_w, tgt_w, K, p2, P2, weight=None
     L = torch.linalg.cholesky(H)
     update = torch.cholesky_solve(b[..., None], L)
     return torch.bmm(se3_exp(update).type(poses.dtype), poses), update
+
+
+# ---------------------------------------------------------------- the solve as the kernel takes it: per SAMPLE
+CHOLESKY, LU, FAILED = "cholesky", "lu", "failed"
+
+
+def solve_branch(H, b):
+    """Which of the three outcomes one sample's 6x6 system takes: ``torch.linalg.cholesky_ex`` (no error, no NaN in the
+    solution) decides the Cholesky path; else ``torch.linalg.solve_ex`` (no error, no NaN in the solution) the LU path;
+    else the solve has failed.  H (6,6), b (6,)."""
+    with torch.no_grad():
+        Lc, info = torch.linalg.cholesky_ex(H)
+        if int(info) == 0 and not torch.isnan(torch.cholesky_solve(b[:, None], Lc)).any():
+            return CHOLESKY
+        x, info = torch.linalg.solve_ex(H, b[:, None])
+        if int(info) == 0 and not torch.isnan(x).any():
+            return LU
+    return FAILED
+
+
+def align_update_per_sample(H, b, poses):
+    """The end of direct_align (utils.py:357-368) with the fall-backs decided per sample -> (new poses (B,4,4), update
+    (B,6,1), the branch of each sample).  Differentiable: each sample's branch is plain torch (``cholesky`` +
+    ``cholesky_solve``; ``linalg.solve``; or the pose passed through with a zero update, which sends no gradient to H / b)."""
+    new, ups, branches = [], [], []
+    for s in range(H.shape[0]):
+        br = solve_branch(H[s].detach(), b[s].detach())
+        branches.append(br)
+        if br == FAILED:
+            new.append(poses[s])
+            ups.append(torch.zeros(6, 1, dtype=H.dtype))
+            continue
+        if br == CHOLESKY:
+            up = torch.cholesky_solve(b[s][:, None], torch.linalg.cholesky(H[s]))
+        else:
+            up = torch.linalg.solve(H[s], b[s][:, None])
+        ups.append(up)
+        new.append(torch.bmm(se3_exp(up[None]).type(poses.dtype), poses[s][None])[0])
+    return torch.stack(new), torch.stack(ups), branches
+
+
+def direct_align_per_sample(poses, src_feat, tgt_feat, src_w, tgt_w, K, p2, P2, weight=None, robust=False, return_branches=False):
+    """What ``mal_direct_align_update`` computes, restated: ``direct_align`` with the solver's fall-backs, decided per
+    SAMPLE -- Cholesky where it succeeds, else LU with partial pivoting, else the sample's pose unchanged with a zero
+    update (``solve_branch``).
+
+    This differs from upstream (utils.py:364-374) on purpose.  Upstream decides per BATCH: ``torch.linalg.cholesky``
+    raises if ANY sample is not positive definite, and then every sample of the batch goes through ``linalg.solve``;
+    if that raises, the whole batch returns ``poses, poses`` (the second being the (B,4,4) poses, not a (B,6,1) update).
+    A kernel thread owns one sample, so a bad sample changes its own row only, and the failed row's update is zero.
+    Where every sample of a batch takes the same branch the two agree; on the Cholesky branch this function equals
+    ``direct_align`` bit for bit in fp32 (tests/test_epipolar_cases.py)."""
+    H, b = normal_equations(src_feat, tgt_feat, src_w, tgt_w, K, p2, P2, weight, robust)
+    new_poses, update, branches = align_update_per_sample(H, b, poses)
+    return (new_poses, update, branches) if return_branches else (new_poses, update)
