@@ -36,6 +36,7 @@ extern "C" {
 #define MAL_MAX_FRAMES 2
 #define MAL_MAX_CAND 4 /* warped -1,+1 and the temporal-hint "syn" -1,+1 (loss_utils.py:79-90) */
 #define MAL_MAX_INSTANCES 64 /* matched instance masks per sample of the temporal-hint producer */
+#define MAL_MATCH_MAX 128    /* instances per side of the temporal-hint producer's matcher (mal_match) */
 
 enum {
   MAL_OK = 0,
@@ -575,7 +576,7 @@ int mal_upsample_bilinear_adjoint(const float* g_out, int B, int h, int w, int H
 
 /* ---- N2: the temporal-hint producer's per-sample arithmetic, manydepth/dyn_utils.py:6-119 --------
  * (fill_dynamic_obj + generate_dynamic_instance), given the matched instance masks of the two warped frames
- * (num,H,W as bytes, non-zero = set; Mask2Former and the matcher stay outside).  Per instance the displacement
+ * (num,H,W as bytes, non-zero = set; Mask2Former stays outside, the matcher is mal_match below).  Per instance the displacement
  * is half the larger-magnitude difference of the bounding-box edges between the frames (rows: low/top, columns:
  * right/left; index 0 is invisible to the extents, as upstream; half-to-even; replace=1 zeroes |d| < 3); "last"
  * patches move by +d, "next" by -d, overlapping copies add, pixels vacated by an instance show the other frame.
@@ -617,6 +618,35 @@ typedef struct mal_dyn_item {
 } mal_dyn_item;
 int mal_dyn_batch_fwd(const mal_dyn_item* items, int n_items, int C, int H, int W, int replace, void* stream);
 int mal_dyn_batch_bwd(const mal_dyn_item* items, int n_items, int C, int H, int W, void* stream);
+
+/* ---- N2, the matcher: HungarianMatcher.memory_efficient_forward, manydepth/matcher.py:89-173 --------------------------
+ * Instances of the two warped frames (n, m) against the confident instances of the target frame (0): masks (num,H,W) as
+ * bytes (MAL_MATCH_U8: bool / uint8, non-zero = set) or float32 (MAL_MATCH_F32: BINARY floats, as Mask2Former emits them,
+ * mask2former/maskformer_model.py:371), classes int64.  C1 (n_n,n_0) / C2 (n_m,n_0) fp32 =
+ *   cost_class [class differs] + cost_dice (1 - (2 sum sigmoid(a) t + 1) / (sum sigmoid(a) + sum t + 1))
+ * formed in fp64 from integer pixel counts (sigmoid(1) as torch's fp32 sigmoid gives it) and rounded once; cost_mask is
+ * accepted and unused, as upstream (:121-122,130), but all three zero is refused (:86).  Each matrix is solved as a
+ * rectangular linear assignment (min(rows, columns) pairs, fp64, shortest augmenting paths: what scipy runs); every
+ * target column j assigned in both problems yields one pair slice_n[k] = row_n(j), slice_m[k] = row_m(j), in ASCENDING j
+ * (upstream: CPython's iteration order of a set).  slice_n / slice_m: MAL_MATCH_MAX int64 each; result: 4 int32 =
+ * count, non-binary (1 if a float32 mask element is neither 0 nor 1: upstream's sigmoid of it has no integer form and
+ * the outputs are not to be used), 0, 0.  An empty side gives count 0.  Three launches and a 16-byte memset on `stream`;
+ * no atomics, bit-reproducible.  ws: mal_match_workspace_bytes.  Sizes beyond MAL_MATCH_MAX are MAL_EINVAL. */
+enum { MAL_MATCH_U8 = 0, MAL_MATCH_F32 = 1 };
+typedef struct mal_match_args {
+  const void* masks_n; const void* masks_m; const void* masks_0;  /* nullable where the count is 0 */
+  int kind_n, kind_m, kind_0;                                     /* MAL_MATCH_U8 / MAL_MATCH_F32 */
+  int n_n, n_m, n_0, H, W;
+  const int64_t* class_n; const int64_t* class_m; const int64_t* class_0;
+  double cost_class, cost_mask, cost_dice;
+  float* C1; float* C2;                 /* out */
+  int64_t* slice_n; int64_t* slice_m;   /* out: the first `count` of MAL_MATCH_MAX slots */
+  int32_t* result;                      /* out: count, non-binary, 0, 0 */
+  void* ws; size_t ws_bytes;
+  void* stream;
+} mal_match_args;
+size_t mal_match_workspace_bytes(int n_n, int n_m, int n_0, int H, int W); /* 0 for sizes mal_match refuses */
+int mal_match(const mal_match_args* args);
 
 /* ---- N3: ManyDepth's cost volume as MAL's student encoder builds it (forward only; upstream runs it under
  * no_grad): manydepth/networks/resnet_encoder.py:152-233 match_features + :296-312 of the encoder's forward.
@@ -763,7 +793,7 @@ int mal_get_option(const char* name, int* value); /* the current value of an opt
  * thread, not on the arming one) and are taken with an atomic exchange: exactly one pass consumes an arm. */
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
 /* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
- * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args;
+ * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args;
  * else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
 

@@ -7,3 +7,14 @@ There is no CPU implementation in this package: without the HIP library and a GP
 operators raise.
 """
 __version__ = "0.1.0"
+
+__all__ = ["HungarianMatcher"]
+
+
+def __getattr__(name):
+    # the temporal-hint producer's matcher (mal_amd/matcher.py); resolved on first use so that `import mal_amd` (and with it
+    # `python -m mal_amd.build`) stays free of torch
+    if name == "HungarianMatcher":
+        from .matcher import HungarianMatcher
+        return HungarianMatcher
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

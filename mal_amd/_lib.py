@@ -119,6 +119,8 @@ SIGNATURES = {
     "mal_eval_mean": (i32, [vp, i32, vp, vp]),
     "mal_eval_errors_workspace_bytes": (sz, [sz]),
     "mal_eval_errors": (i32, [vp, i32, vp, i32, sz, vp, vp, sz, vp]),
+    "mal_match_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "mal_match": (i32, [vp]),
 }
 
 class DynItem(C.Structure):
@@ -200,7 +202,17 @@ class EvalArgs(C.Structure):
                 [(n, vp) for n in ("seg", "idx", "gt", "disp", "pred", "img_out", "stream")])
 
 
+class MatchArgs(C.Structure):
+    """mal_match_args (include/mal_hip.h)."""
+    _fields_ = ([(n, vp) for n in ("masks_n", "masks_m", "masks_0")] +
+                [(n, i32) for n in ("kind_n", "kind_m", "kind_0", "n_n", "n_m", "n_0", "H", "W")] +
+                [(n, vp) for n in ("class_n", "class_m", "class_0")] +
+                [(n, C.c_double) for n in ("cost_class", "cost_mask", "cost_dice")] +
+                [(n, vp) for n in ("C1", "C2", "slice_n", "slice_m", "result", "ws")] + [("ws_bytes", sz), ("stream", vp)])
+
+
 DR_MAX_ITERS = 4
+MATCH_MAX, MATCH_U8, MATCH_F32 = 128, 0, 1
 DR_NO_AUTOMASK, DR_NO_MOTION_MASK, DR_NOISE_PHILOX, DR_AVG, DR_NO_SSIM, DR_POSE_UPDATE = 1, 2, 4, 8, 16, 32
 DR_POSE_NOISE_KEY = 0x706f73655f757064
 MS_MAX_SCALES = 4
@@ -234,7 +246,7 @@ def load():
         fn.argtypes = args
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
-    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs)):
+    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

@@ -28,6 +28,7 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 4: return sizeof(mal_step_scales_args);
     case 5: return sizeof(mal_eval_seg);
     case 6: return sizeof(mal_eval_args);
+    case 7: return sizeof(mal_match_args);
     default: return 0;
   }
 }

@@ -1,6 +1,6 @@
 // N2: the temporal-hint producer's per-sample arithmetic -- manydepth/dyn_utils.py:6-119,
 // `fill_dynamic_obj` + `generate_dynamic_instance` -- given the matched instance masks of the two warped
-// frames.  (Mask2Former and the Hungarian matcher that produce the masks stay outside this library.)
+// frames.  (Mask2Former, which produces the masks, stays outside this library; the Hungarian matcher is mal_match.hip.)
 //
 // Upstream this is a TorchScript loop over instances with (num, 3, H, W) temporaries per call and per
 // sample; here it is two launches for up to 16 samples and no temporaries (the scalar kernels first; the 16-byte /

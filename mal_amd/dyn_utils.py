@@ -2,7 +2,8 @@
 (``generate_dynamic_instance`` / ``fill_dynamic_obj``, :6-119) on the device as three HIP launches instead of a
 TorchScript loop over instances with (num,3,H,W) temporaries.  Same names and signatures as the reference, so
 ``from manydepth.dyn_utils import image_synthesis`` can point here; the instance segmenter (Mask2Former through
-``generate_instances``) and the Hungarian matcher stay external and are passed in exactly as upstream.
+``generate_instances``) stays external; the Hungarian matcher is ``mal_amd.matcher.HungarianMatcher`` (or upstream's); both
+are passed in exactly as upstream.
 """
 from __future__ import annotations
 

@@ -103,7 +103,9 @@ class StageTimer:
 class TrainHarness:
     def __init__(self, opt, device, process_group=None, image_synthesis=None, exchange_segments=4):
         """``image_synthesis(inputs, outputs, scale) -> has_ins``: the temporal hint's producer (``--temporal``; upstream
-        binds dyn_utils.image_synthesis to the segmenter and the matcher, trainer.py:1161-1165).  ``exchange_segments``:
+        binds dyn_utils.image_synthesis to the segmenter and the matcher, trainer.py:1161-1165; here
+        ``lambda i, o, s: dyn_utils.image_synthesis(i, o, s, thres, ins_model, matcher=mal_amd.matcher.HungarianMatcher())``
+        with the matcher built once).  ``exchange_segments``:
         pieces of the flat gradient buffer that are all-reduced from inside the backward (1 = one all-reduce after it)."""
         self.opt, self.device = opt, torch.device(device)
         self.image_synthesis = image_synthesis
