@@ -125,7 +125,8 @@ __global__ __launch_bounds__(64) void match_cost_kernel(MatchParams p) {
   }
 }
 
-// value of a per-lane pair of registers (element e lives in lane e & 63, register e >> 6) at a wave-uniform index
+// value of a per-lane pair of registers (element e lives in lane e & 63, register e >> 6) at index e (wave-uniform or
+// per lane); call it where the whole wave is active
 template <typename T>
 MAL_DEV T match_at(const T (&r)[2], int e) {
   const T lo = __shfl(r[0], e & 63, 64), hi = __shfl(r[1], e & 63, 64);
@@ -178,8 +179,11 @@ MAL_DEV void match_solve(const float* C, int nr, int nc, int si, int sj, int (&c
     for (int k = 0; k < 2; ++k) {
       const int row = lane + 64 * k, c = col_of[k];
       const int cc = c < 0 ? 0 : c;
-      const double spc_c = (cc & 64) ? __shfl(spc[1], cc & 63, 64) : __shfl(spc[0], cc & 63, 64);
-      const int sc_c = (cc & 64) ? __shfl((int)sc[1], cc & 63, 64) : __shfl((int)sc[0], cc & 63, 64);
+      // (both registers are read by EVERY lane and selected afterwards: a shuffle inside a branch on the lane's own column
+      // would read from lanes the branch has switched off)
+      const int sci[2] = {(int)sc[0], (int)sc[1]};
+      const double spc_c = match_at(spc, cc);
+      const int sc_c = match_at(sci, cc);
       if (row == cur) u[k] += min_val;
       else if (c >= 0 && sc_c) u[k] += min_val - spc_c;
     }

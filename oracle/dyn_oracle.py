@@ -18,6 +18,14 @@ Stated per output pixel p = (r, c) rather than as slice assignments:
         bg(p)  = img_next(p) where or_i (mask_last_i & ~mask_next_i)(p), else img_last(p)
         ori_last(p) = (any(p) ? A(p) : bg(p)) where or_i (mask_last_i | mask_next_i)(p), else img_last(p)
     and symmetrically for "next" with -d_i, mask_next, and the roles of the images swapped.
+
+Summation order (the contract the kernels share): A(p) is accumulated in fp32 IN INSTANCE ORDER, i = 0, 1, ... .  The
+reference forms it as ``img_mv.sum(dim=0)`` over a (num, C, H, W) stack, which torch adds sequentially for up to 16 terms
+and in a cascade above that.  "Bit-exact against the reference" therefore holds for num <= 16 whatever the images, and for
+num up to 64 only where the sum does not depend on the order (images that are multiples of 1/256: every partial sum is
+exact).  With 20 overlapping copies of k/255 images this restatement and the reference differ in the last bits, by at most
+(n - 1) ulp of the sum on a pixel that n copies reach; tests/golden/dyn_edges_k256_24x40.npz and
+dyn_order_k255_n20_24x40.npz (oracle/gen_golden_dyn.order_cases, tests/test_dyn_cases.py) pin both statements.
 """
 from __future__ import annotations
 

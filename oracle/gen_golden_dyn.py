@@ -135,6 +135,42 @@ def synthesis_case():
     assert changed == [False, True, False, True]
 
 
+def order_cases():
+    """The summation-order contract (oracle/dyn_oracle.py): two fixtures at 24x40 with 20 instances on top of each other.
+    ``dyn_edges_k256_24x40``: the crafted instances of tests/dyn_checks.py plus the 20, images k/256 -- sums exact in any
+    order; ``dyn_order_k255_n20_24x40``: the 20 alone, images k/255 -- the reference's cascaded sum above 16 terms shows.
+    The crafted instances and the mask generator are those of the test table (``tests.dyn_checks.crafted_boxes`` /
+    ``box_masks``): after an edit of either, regenerate ``dyn_edges_k256_24x40`` with this function and commit it with the
+    edit (tests/test_dyn_cases.py holds the fixture's instance count to the table's)."""
+    sys.path.insert(0, REF)
+    import manydepth.dyn_utils as DU
+    from tests import dyn_checks as K
+    H, W = 24, 40
+    grid_h, grid_w = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    pile = [((4, 15, 8, 25), (6, 17, 10, 27))] * 20
+    for tag, den, with_edges in (("dyn_edges_k256_24x40", 256, True), ("dyn_order_k255_n20_24x40", 255, False)):
+        rng = np.random.default_rng(len(tag))
+        ml, mn = K.box_masks(H, W, pile, rng, density=0.95)
+        if with_edges:
+            el, en = K.box_masks(H, W, K.crafted_boxes(H, W), rng)
+            ml, mn = torch.cat([el, ml]), torch.cat([en, mn])
+        k_last, k_next = (rng.integers(0, 255, (3, H, W)).astype(np.uint8) for _ in range(2))
+        il = (torch.from_numpy(k_last.astype(np.float32)) / den).requires_grad_(True)
+        inx = (torch.from_numpy(k_next.astype(np.float32)) / den).requires_grad_(True)
+        ct_l, ct_n = (torch.from_numpy(np.round(rng.standard_normal((3, H, W)) * 64).astype(np.float32) / 64) for _ in range(2))
+        d = {"in/mask_last": ml.numpy(), "in/mask_next": mn.numpy(), "in/img_last": k_last, "in/img_next": k_next,
+             "in/denominator": np.int64(den), "in/ct_last": ct_l.numpy(), "in/ct_next": ct_n.numpy()}
+        for replace in ((False, True) if with_edges else (False,)):
+            ol, on = DU.generate_dynamic_instance(grid_h, grid_w, ml, mn, il, inx, replace)
+            gl, gn = torch.autograd.grad((ol * ct_l).sum() + (on * ct_n).sum(), [il, inx])
+            sfx = "_replace" if replace else ""
+            d.update({"out/ori_last" + sfx: ol.detach().numpy(), "out/ori_next" + sfx: on.detach().numpy(),
+                      "out/g_img_last" + sfx: gl.numpy(), "out/g_img_next" + sfx: gn.numpy()})
+        np.savez_compressed(os.path.join(OUT, tag + ".npz"), **d)
+        print(tag, tuple(ml.shape), os.path.getsize(os.path.join(OUT, tag + ".npz")), "bytes")
+
+
 if __name__ == "__main__":
     main()
     synthesis_case()
+    order_cases()

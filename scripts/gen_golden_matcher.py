@@ -86,20 +86,7 @@ def make_inputs(rng, H, W, n_n, n_m, n_0, classes_differ):
     return sides[0], sides[1], (tgt, cls_0.astype(np.int64))
 
 
-def margin_of(C):
-    """smallest increase in the optimal total cost when one chosen edge is forbidden (fp64)"""
-    C = np.asarray(C, dtype=np.float64)
-    if C.size == 0:
-        return np.inf
-    rows, cols = R.linear_sum_assignment(C)
-    best = C[rows, cols].sum()
-    worst = np.inf
-    for i, j in zip(rows, cols):
-        D = C.copy()
-        D[i, j] = 1e6
-        r2, c2 = R.linear_sum_assignment(D)
-        worst = min(worst, D[r2, c2].sum() - best)
-    return worst
+margin_of = R.margin_of
 
 
 def run_reference(M, n, m, t, H, W):

@@ -83,14 +83,18 @@ def costs_fp64(masks_a, masks_t, class_a, class_t, cost_class=1.0, cost_dice=1.0
     return cost_class * differ + cost_dice * dice
 
 
-def linear_sum_assignment(C):
+def linear_sum_assignment(C, return_duals=False):
     """Rectangular assignment by shortest augmenting paths with duals (Crouse 2016, the algorithm scipy runs), fp64.
-    Returns (row_ind, col_ind), sorted by row, min(rows, cols) pairs."""
+    Returns (row_ind, col_ind), sorted by row, min(rows, cols) pairs.  The rule mal_match.hip states and follows: the
+    reduced cost ``min_val + C[i, j] - u[i] - v[j]`` is formed in fp64 in that order, and of several columns at the minimum the
+    LOWEST INDEX is scanned next.  ``return_duals``: also (u, v) in the orientation of ``C`` (one per row, one per column;
+    the duals of the side that is augmented over are free, those of the other side are <= 0)."""
     C = np.asarray(C, dtype=np.float64)
     if C.ndim != 2:
         raise ValueError("expected a matrix")
     if C.size == 0:
-        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        empty = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        return empty + (np.zeros(C.shape[0]), np.zeros(C.shape[1])) if return_duals else empty
     transpose = C.shape[1] < C.shape[0]
     if transpose:
         C = C.T
@@ -131,8 +135,44 @@ def linear_sum_assignment(C):
     rows, cols = np.arange(nr, dtype=np.int64), col4row.astype(np.int64)
     if transpose:
         order = np.argsort(cols)
-        return cols[order], rows[order]
-    return rows, cols
+        rows, cols, u, v = cols[order], rows[order], v, u
+    return (rows, cols, u, v) if return_duals else (rows, cols)
+
+
+def certify(C, rows, cols, u, v, tol=1e-12):
+    """The optimality certificate of an assignment (complementary slackness of the assignment LP), stated for the side the
+    solver augments over as "rows": u_i + v_j <= C_ij + tol everywhere with equality (within tol) on the assigned edges,
+    v <= 0, v = 0 on unassigned columns; every row assigned once, the columns distinct.  Returns the duality gap
+    sum C[assigned] - (sum u + sum v) (zero up to rounding for an optimum)."""
+    C = np.asarray(C, dtype=np.float64)
+    rows, cols, u, v = np.asarray(rows), np.asarray(cols), np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    if C.shape[1] < C.shape[0]:
+        C, rows, cols, u, v = C.T, cols, rows, v, u
+    nr, nc = C.shape
+    assert len(rows) == nr and sorted(rows.tolist()) == list(range(nr)) and len(set(cols.tolist())) == nr
+    assert C.size == 0 or float((u[:, None] + v[None, :] - C).max()) <= tol
+    assert float(np.abs(u[rows] + v[cols] - C[rows, cols]).max(initial=0.0)) <= tol
+    assert float(v.max(initial=0.0)) <= 0.0
+    free = np.ones(nc, bool)
+    free[cols] = False
+    assert not v[free].any()
+    return float(C[rows, cols].sum() - u.sum() - v.sum())
+
+
+def margin_of(C):
+    """smallest increase in the optimal total cost when one chosen edge is forbidden (fp64)"""
+    C = np.asarray(C, dtype=np.float64)
+    if C.size == 0:
+        return np.inf
+    rows, cols = linear_sum_assignment(C)
+    best = C[rows, cols].sum()
+    worst = np.inf
+    for i, j in zip(rows, cols):
+        D = C.copy()
+        D[i, j] = 1e6
+        r2, c2 = linear_sum_assignment(D)
+        worst = min(worst, D[r2, c2].sum() - best)
+    return worst
 
 
 def intersect(idx_n, idx_0, idx_m, idx_1):

@@ -137,3 +137,75 @@ def test_host_side_of_the_matcher(lib):
         m(inst, inst, inst)
     with pytest.raises(_lib.MalError):
         m.memory_efficient_forward(inst, inst, inst)
+
+
+# ---------------------------------------------------------------- the sweep's case table (tests/matcher_checks.py)
+def test_sweep_table_holds_the_sizes_shapes_and_inputs_of_the_design():
+    from tests import matcher_checks as K
+    specs = list(K.CASES.values())
+    assert set(K.REQUIRED_SIZES) <= {c["sizes"] for c in specs}
+    assert {k for k in range(3)} == {k for c in specs for k in range(3) if c["sizes"][k] == 0 and sum(c["sizes"]) > 0}
+    assert set(K.REQUIRED_SHAPES) <= {(c["H"], c["W"]) for c in specs}
+    assert K.nw(96, 96) == 144 > 16 * 8 and K.nw(50, 173) == 136 and (50 * 173) % 64 == 10 and K.nw(5, 13) == 2
+    assert {"rand", "proto", "ellipse"} == {c["gen"] for c in specs}
+    assert {"equal", "distinct", "high", "mixed"} == {c["classes"] for c in specs}
+    assert {(1.0, 1.0, 1.0), (0.0, 1.0, 1.0), (1.0, 1.0, 0.0)} == {c["weights"] for c in specs}
+    assert any(len(set(c["kinds"])) == 3 for c in specs) and all(set(c["kinds"]) <= set(K.KINDS) for c in specs)
+    big = [c for c in specs if min(c["sizes"]) > 64]
+    assert len(big) >= 3  # a lane owns a row and a column in two registers
+    d = K.make("rand_128x128x128_96x96_second_pack_trip")
+    for s in ("n", "m", "0"):
+        counts = d["masks_" + s].reshape(128, -1).sum(1)
+        assert counts.min() == 0 and counts.max() == 96 * 96  # an empty and a full mask among the instances
+        assert set(np.unique(d["bytes_" + s]).tolist()) == set(K.MASK_BYTES)
+    hi = K.make("rand_128x128x128_50x173_dice_weight_zero")
+    both = np.concatenate([hi["class_n"], hi["class_0"]])
+    assert len(np.unique(both)) > 1 and len(np.unique(both.astype(np.int32))) == 1  # differ above bit 32 only
+    D1, _ = K.reference("rand_128x128x128_50x173_dice_weight_zero")
+    assert set(np.unique(D1).tolist()) <= {0.0, 1.0}  # the cost is 0 / 1: every path a tie
+    dist = K.make("rand_70x100x128_5x13")
+    assert len(np.unique(np.concatenate([dist["class_n"], dist["class_m"], dist["class_0"]]))) == 70 + 100 + 128
+
+
+def _scipy_lsa():
+    try:
+        from scipy.optimize import linear_sum_assignment
+        return linear_sum_assignment
+    except Exception:
+        return None
+
+
+@pytest.mark.parametrize("name", __import__("tests.matcher_checks", fromlist=["CASES"]).CASES)
+def test_restated_solver_is_certified_on_every_sweep_matrix(name):
+    """complementary slackness: u_i + v_j <= C_ij + 1e-12 everywhere, equality on the assigned edges, v <= 0 and v = 0 on
+    unassigned columns -- on the fp64 matrices and on their fp32 roundings (what the kernel hands to its solver)"""
+    from tests import matcher_checks as K
+    lsa = _scipy_lsa()
+    for D in K.reference(name):
+        for C in (D, D.astype(np.float32).astype(np.float64)):
+            rows, cols, u, v = R.linear_sum_assignment(C, return_duals=True)
+            assert len(rows) == min(C.shape)
+            if C.size == 0:
+                continue
+            gap = R.certify(C, rows, cols, u, v)
+            assert abs(gap) <= 1e-9
+            if lsa is not None:
+                r2, c2 = lsa(C)
+                assert abs(R.assignment_cost(C, rows, cols) - float(C[r2, c2].sum())) <= 1e-9
+    if K.CASES[name]["unique"]:
+        D1, D2 = K.reference(name)
+        for D in (D1, D2):
+            F = D.astype(np.float32).astype(np.float64)
+            assert R.margin_of(D) >= K.MARGIN and R.margin_of(F) >= K.MARGIN
+        assert np.array_equal(R.match(D1, D2)[0], R.match(D1.astype(np.float32), D2.astype(np.float32))[0])
+
+
+def test_certificate_refuses_a_suboptimal_assignment():
+    C = np.array([[1.0, 2.0, 9.0], [2.0, 1.0, 9.0]])
+    rows, cols, u, v = R.linear_sum_assignment(C, return_duals=True)
+    assert cols.tolist() == [0, 1] and R.certify(C, rows, cols, u, v) == 0.0
+    with pytest.raises(AssertionError):
+        R.certify(C, rows, np.array([1, 0]), u, v)
+    rows, cols, u, v = R.linear_sum_assignment(C.T, return_duals=True)  # transposed: the duals come back in C's orientation
+    assert rows.tolist() == [0, 1] and cols.tolist() == [0, 1] and len(u) == 3 and len(v) == 2
+    assert R.certify(C.T, rows, cols, u, v) == 0.0
