@@ -37,6 +37,9 @@ extern "C" {
 #define MAL_MAX_CAND 4 /* warped -1,+1 and the temporal-hint "syn" -1,+1 (loss_utils.py:79-90) */
 #define MAL_MAX_INSTANCES 64 /* matched instance masks per sample of the temporal-hint producer */
 #define MAL_MATCH_MAX 128    /* instances per side of the temporal-hint producer's matcher (mal_match) */
+#define MAL_INSTANCES_MAX_QK 16384 /* mal_instances: queries x classes (Q*K) per image; Q=200, K=80 is 16000 */
+#define MAL_INSTANCES_MAX_K1 1025  /* mal_instances: logits per query (K+1) */
+#define MAL_INSTANCES_MAX_N 65535  /* mal_instances: images per call */
 
 enum {
   MAL_OK = 0,
@@ -648,6 +651,40 @@ typedef struct mal_match_args {
 size_t mal_match_workspace_bytes(int n_n, int n_m, int n_0, int H, int W); /* 0 for sizes mal_match refuses */
 int mal_match(const mal_match_args* args);
 
+/* ---- N2, the segmenter's tail: Mask2Former's instance inference, mask2former/maskformer_model.py:219-227 + :344-380 ----
+ * pred_logits (N,Q,K+1) and pred_masks (N,Q,h,w) fp32 as the network returns them -> per image the `topk` best (query,
+ * class) pairs with their full-size BINARY masks as bytes, what mal_match and mal_dyn_batch_* read.  No float plane is
+ * written.  Output size (H,W): 4(h-1) < H <= 4h and likewise W, the crop of the x4 plane to the image (upstream pads its
+ * input to a multiple of 32 and the mask features sit at stride 4, so F.interpolate(mode="bilinear", align_corners=False)
+ * is always exactly x4 there); any other size is MAL_EINVAL.
+ * Selection: p = softmax over the K+1 logits of a query (fp64 inside, rounded once to fp32), last column dropped; the
+ * topk largest of the Q*K values in DESCENDING p, ties by ASCENDING flat index q*K + c (upstream's topk(sorted=False)
+ * leaves the order open); then the optional thing filter (thing[c] != 0 keeps class c, :360-367), survivors compacted
+ * in order -> count[n] slots.  The same query may fill several slots; each slot has its own mask.
+ * Masks: v = x4 bilinear value (ATen's rule: source = max((o + 0.5)/4 - 0.5, 0), neighbour clamped), byte = v > 0.
+ * mask_score = float(sum of sigmoid(v) over the set pixels, fp64 partials in a fixed order) / (float(set pixels) + 1e-6f),
+ * 0 for an empty mask; score = cls_score * mask_score (fp32).  Slots from count[n] on: classes 0, query -1, scores 0,
+ * masks not written.  Bounds: 1 <= topk <= min(Q*K, MAL_MATCH_MAX), Q*K <= MAL_INSTANCES_MAX_QK, K+1 <=
+ * MAL_INSTANCES_MAX_K1, N <= MAL_INSTANCES_MAX_N, h*w <= 2^24.  Three launches on `stream`; no allocation, no readback, no
+ * float atomics, bit-reproducible.  ws: mal_instances_workspace_bytes. */
+typedef struct mal_instances_args {
+  const float* pred_logits;  /* (N,Q,K+1) */
+  const float* pred_masks;   /* (N,Q,h,w) */
+  const uint8_t* thing;      /* K bytes, nullable: keep every class */
+  int N, Q, K, h, w, H, W, topk;
+  int32_t* count;            /* out (N) */
+  uint8_t* masks;            /* out (N,topk,H,W), 0 or 1 */
+  float* scores;             /* out (N,topk) */
+  int64_t* classes;          /* out (N,topk) */
+  int32_t* query;            /* out (N,topk) */
+  float* cls_score;          /* out (N,topk) */
+  float* mask_score;         /* out (N,topk) */
+  void* ws; size_t ws_bytes;
+  void* stream;
+} mal_instances_args;
+size_t mal_instances_workspace_bytes(int N, int Q, int K, int h, int w, int H, int W, int topk); /* 0 for sizes mal_instances refuses */
+int mal_instances(const mal_instances_args* args);
+
 /* ---- N3: ManyDepth's cost volume as MAL's student encoder builds it (forward only; upstream runs it under
  * no_grad): manydepth/networks/resnet_encoder.py:152-233 match_features + :296-312 of the encoder's forward.
  * current_feats (B,C,h,w) and lookup_feats (B,F,C,h,w) planar as the encoder produces them, C = 64 (with option
@@ -793,7 +830,7 @@ int mal_get_option(const char* name, int* value); /* the current value of an opt
  * thread, not on the arming one) and are taken with an atomic exchange: exactly one pass consumes an arm. */
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
 /* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
- * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args;
+ * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args, 8 mal_instances_args;
  * else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
 

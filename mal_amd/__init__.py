@@ -8,7 +8,7 @@ operators raise.
 """
 __version__ = "0.1.0"
 
-__all__ = ["HungarianMatcher"]
+__all__ = ["HungarianMatcher", "InstanceSegmenter", "Instances", "instance_inference"]
 
 
 def __getattr__(name):
@@ -17,4 +17,8 @@ def __getattr__(name):
     if name == "HungarianMatcher":
         from .matcher import HungarianMatcher
         return HungarianMatcher
+    # the segmenter's inference tail (mal_amd/instances.py), resolved the same way
+    if name in ("InstanceSegmenter", "Instances", "instance_inference"):
+        from . import instances
+        return getattr(instances, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -121,6 +121,8 @@ SIGNATURES = {
     "mal_eval_errors": (i32, [vp, i32, vp, i32, sz, vp, vp, sz, vp]),
     "mal_match_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "mal_match": (i32, [vp]),
+    "mal_instances_workspace_bytes": (sz, [i32] * 8),
+    "mal_instances": (i32, [vp]),
 }
 
 class DynItem(C.Structure):
@@ -211,6 +213,14 @@ class MatchArgs(C.Structure):
                 [(n, vp) for n in ("C1", "C2", "slice_n", "slice_m", "result", "ws")] + [("ws_bytes", sz), ("stream", vp)])
 
 
+class InstancesArgs(C.Structure):
+    """mal_instances_args (include/mal_hip.h)."""
+    _fields_ = ([(n, vp) for n in ("pred_logits", "pred_masks", "thing")] +
+                [(n, i32) for n in ("N", "Q", "K", "h", "w", "H", "W", "topk")] +
+                [(n, vp) for n in ("count", "masks", "scores", "classes", "query", "cls_score", "mask_score", "ws")] +
+                [("ws_bytes", sz), ("stream", vp)])
+
+
 DR_MAX_ITERS = 4
 MATCH_MAX, MATCH_U8, MATCH_F32 = 128, 0, 1
 DR_NO_AUTOMASK, DR_NO_MOTION_MASK, DR_NOISE_PHILOX, DR_AVG, DR_NO_SSIM, DR_POSE_UPDATE = 1, 2, 4, 8, 16, 32
@@ -246,7 +256,7 @@ def load():
         fn.argtypes = args
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
-    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs)):
+    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs, InstancesArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

@@ -29,6 +29,7 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 5: return sizeof(mal_eval_seg);
     case 6: return sizeof(mal_eval_args);
     case 7: return sizeof(mal_match_args);
+    case 8: return sizeof(mal_instances_args);
     default: return 0;
   }
 }
