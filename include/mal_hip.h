@@ -798,9 +798,14 @@ int mal_direct_align_update_bwd(const float* H, const float* b, const float* pos
  * "step_overlap" [0..2] 1 (default): with MAL_STEP_TEMPORAL the ensemble pass runs on a side stream beside the producer
  *               (forked after the warp pass, joined before the student pass; events, capturable); 0: in line; 2: beside the
  *               fused sweep (slower: kept for A/B);
- * "student_overlap" 0|1 (default 1): with MAL_STEP_TEMPORAL the student's marching pass (without its consistency /
+ * "student_overlap" [0..2] (default 2): with MAL_STEP_TEMPORAL the student's marching pass (without its consistency /
  *               distillation epilogue, which becomes a pointwise launch after the join) is forked beside the producer behind
- *               the ensemble pass; 0: in line after the fused sweep, epilogue inside the pass (kept for A/B);
+ *               the ensemble pass; 2: the two forked passes are ONE launch that runs only the samples whose weight
+ *               1 - augmentation mask is not zero (decided on the device at run time; an augmented sample's terms are exact
+ *               zeros) -- only when the step returns none of multi_reproj, ens_reproj, consistency_mask_out, dec_student and
+ *               runs without MAL_STEP_MAIN_TEMPORAL, MAL_STEP_DUAL_DISTIL, ens_disp, with B <= 64; otherwise as 1;
+ *               1: a launch each, every sample computed (same-binary A/B); 0: in line after the fused sweep, epilogue
+ *               inside the pass (kept for A/B);
  * "side_order"  0|1 (default 0): 1 = of the forked passes the student's goes first, the ensemble pass behind it (slower);
  * "side_priority" 0|1 (default 0): 1 = the side stream is created with the device's lowest priority (slower); read only when
  *               a caller stream's side stream is first created;

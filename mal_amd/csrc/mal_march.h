@@ -103,6 +103,15 @@ MarchParams march_params(int B, int H, int W, float min_depth, float max_depth, 
 // fills the task decomposition for `flags` (MAL_F_*), launches the matching instantiation on `st`
 // (bracketed by the one-shot profile events if armed).  Partials go to p.block_sums / p.block_gP.
 int march_launch(MarchParams& p, int flags, hipStream_t st);
+// The two passes a --temporal step forks beside the producer -- the ensemble pass (`ens`, forward only; nullptr with
+// --no_ens) and the student's gradient pass without its epilogue (`stu`) -- as ONE launch that runs only the tasks of the
+// samples whose per-sample scale (stu.sample_scale, decided on the device from the tensor's contents at run time) is not
+// exactly zero: such a sample's terms are all multiplied by that zero.  The dead samples' rows of stu.g_reproj, their
+// boundary scratch rows and their records in stu.block_sums are zero-filled; their rows of the two passes' min_reproj maps
+// are NOT written (the caller must not read them).  stu_first: which sub-pass takes the leading workgroups.  B <= 64.
+// march_pair_qualifies: whether the options / shape allow it (march_pair_launch returns MAL_EINVAL otherwise).
+bool march_pair_qualifies(int B, int H, int W);
+int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStream_t st);
 // the decomposition march_launch picks for (B,H,W) and `flags` on the current device
 void march_geometry(int B, int H, int W, int flags, int* strips, int* segs, int* rows);
 // the one-call steps: the first call of a step records the decomposition it uses for workspace `ws`; the later calls check

@@ -337,8 +337,12 @@ enum : int {
 #ifndef MAL_FIN_UNIFORM
 #define MAL_FIN_UNIFORM 1
 #endif
+// the parameter block as the body reads it: in the kernarg segment (constant address space, scalar loads)
+typedef __attribute__((address_space(4))) const MarchParams CMarchParams;
+// kp0: the launch's parameter block inside the kernarg segment (a merged launch holds more than one: march_pair_kernel);
+// task: the wave's task, (sample, segment, strip) = (task / (strips * segs), ...), in [0, ntasks) or beyond (nothing to do)
 template <bool GRAD, bool AUTOMASK, bool POSE, bool EPI, bool DBG, bool TEMPORAL, bool EXPORT, int SPEC = 0>
-MAL_DEV void march_body() {
+MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
   constexpr bool LEAN = (SPEC & kSpecLean) != 0, NO_DISP2 = (SPEC & kSpecNoDisp2) != 0;
   // --avg_reprojection / --no_ssim (MarchParams::avg, ::no_ssim, wave-uniform): in the generic gradient passes only, so that
   // no instantiation a whole-step list of the default options launches carries the tests
@@ -360,12 +364,9 @@ MAL_DEV void march_body() {
   // The ~30 pointers and sizes of the parameter block do not fit in scalar registers next to the loop
   // state; rather than let them spill (v_readlane reloads in the row loop) every iteration re-reads the
   // fields it uses from the kernarg segment with scalar loads, through a pointer made opaque per iteration.
-  typedef __attribute__((address_space(4))) const MarchParams CParams;
-  CParams* const kp0 = (CParams*)__builtin_amdgcn_kernarg_segment_ptr();
+  typedef CMarchParams CParams;
   CParams& p = *kp0;
 
-  const int id = blockIdx.x;
-  const int task = (id & 7) * p.per_xcd + (id >> 3);
   if (task >= p.ntasks) return;
   const int per_b = p.strips * p.segs;
   const int b = task / per_b;
@@ -1253,6 +1254,14 @@ MAL_DEV void march_body() {
   }
 }
 
+// one pass per launch: the parameter block is the kernel's only argument, the tasks are dealt to the workgroups in
+// XCD-striped order -- consecutive tasks (a sample's strips and segments) share an XCD and its L2
+template <bool GRAD, bool AUTOMASK, bool POSE, bool EPI, bool DBG, bool TEMPORAL, bool EXPORT, int SPEC = 0>
+MAL_DEV void march_body() {
+  CMarchParams* const kp0 = (CMarchParams*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int id = blockIdx.x;
+  march_body<GRAD, AUTOMASK, POSE, EPI, DBG, TEMPORAL, EXPORT, SPEC>(kp0, (id & 7) * kp0->per_xcd + (id >> 3));
+}
 // the parameter block is read from the kernarg segment inside the body (see there)
 template <bool GRAD, bool AUTOMASK, bool POSE, bool EPI, bool DBG = false, bool TEMPORAL = false>
 __global__ __launch_bounds__(64, 2) void march_kernel(MarchParams p_kernarg) {
@@ -1301,6 +1310,80 @@ __global__ __launch_bounds__(64, 2) void march_framed_kernel(MarchParams p_kerna
 // ... specialised like the other passes of the one-call lists (packed texels, no mask operands): what mal_dr_loss_fwd launches
 __global__ __launch_bounds__(64, 2) void march_framed_lean_kernel(MarchParams p_kernarg) {
   march_body<true, true, true, false, false, false, false, kSpecFramed | kSpecLean | kSpecExtNo | kSpecCostNo | kSpecNoScale>();
+}
+
+// ---- the two forked passes of the --temporal step as ONE launch over the LIVE samples' tasks (march_pair_launch)
+// The ensemble pass (forward only) and the student's pass without its epilogue depend on nothing of each other.  A sample
+// whose per-sample scale (1 - augmentation mask) is exactly 0 contributes exact zeros to everything either pass leaves for
+// the loss, so its tasks are not run: every wave reads the B scales itself (one load, one ballot -- the device decides, a
+// replayed graph follows the tensor's current contents), the live samples' tasks are compacted into the leading workgroups of
+// each sub-pass in the same XCD-striped order, and the surplus workgroups of the student's sub-pass store the zeros the dead
+// tasks would have left (gradient rows, boundary scratch rows, the sums' record) so that no consumer reads stale memory.
+// No inter-workgroup hand-off: a workgroup's work depends on its index and the scale tensor only.
+struct MarchPairParams { MarchParams ens, stu; int ens_blocks, stu_blocks, stu_first; };
+
+// sample number of the k-th set bit of `mask` (k < popcount, wave-uniform)
+MAL_DEV int nth_sample(unsigned long long mask, int k, int lane) {
+  const bool mine = ((mask >> lane) & 1ull) != 0 && __popcll(mask & ((1ull << lane) - 1ull)) == k;
+  return (int)__builtin_ctzll(__ballot(mine));
+}
+// what task `task` of the student's pass leaves when every weight of its sample is zero
+MAL_DEV void march_zero_task(CMarchParams* const kp, const int task) {
+  CMarchParams& p = *kp;
+  constexpr int HALO = 2, CW = 64 - 2 * HALO;
+  const int per_b = p.strips * p.segs, b = task / per_b, tt = task - b * per_b;
+  const int seg = tt / p.strips, strip = tt - seg * p.strips;
+  const int H = p.H, W = p.W, lane = threadIdx.x;
+  const int gx = strip * CW - HALO + lane;
+  const int ph_lo = seg * p.rows, ph_hi = min(ph_lo + p.rows, H);
+  if (gx >= 0 && gx < W && lane >= HALO && lane < 64 - HALO) {
+    float* const g = p.g_reproj + (size_t)b * H * W + gx;
+    for (int y = ph_lo; y < ph_hi; ++y) g[(size_t)y * W] = 0.f;
+    if (p.bnd) {  // the neighbouring segments' boundary rows this task completes (one-row halo)
+      if (ph_lo > 0) p.bnd[((size_t)(b * p.segs + seg - 1) * 2 + 1) * W + gx] = 0.f;
+      if (ph_hi < H) p.bnd[((size_t)(b * p.segs + seg + 1) * 2 + 0) * W + gx] = 0.f;
+    }
+  }
+  if (lane < 4) p.block_sums[(size_t)task * 8 + lane] = 0.0;
+}
+__global__ __launch_bounds__(64, 2) void march_pair_kernel(MarchPairParams pk_kernarg) {
+  typedef __attribute__((address_space(4))) const MarchPairParams CPair;
+  CPair* const pk = (CPair*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int lane = threadIdx.x;
+  // the sub-pass of this workgroup (wave-uniform): option "side_order" decides which one holds the leading workgroups
+  const int first = pk->stu_first ? pk->stu_blocks : pk->ens_blocks;
+  const bool in_first = (int)blockIdx.x < first;
+  const bool student = in_first == (pk->stu_first != 0);
+  const int id = in_first ? (int)blockIdx.x : (int)blockIdx.x - first;
+  CMarchParams* const kp = student ? &pk->stu : &pk->ens;
+  // the live samples: scale != 0, as the student's pass forms it (march_body: sscale)
+  const int B = pk->stu.B;
+  float sc = 1.0f;
+  if (lane < B) {
+    const float v = pk->stu.sample_scale[lane];
+    sc = pk->stu.sample_scale_is_mask ? 1.0f - v : v;
+  }
+  const unsigned long long all = B >= 64 ? ~0ull : (1ull << B) - 1ull;
+  const unsigned long long live = __ballot(lane < B && !(sc == 0.0f)) & all;
+  const int per_b = kp->strips * kp->segs;
+  const int n_live = __popcll(live) * per_b;       // live tasks of this sub-pass
+  const int per_xcd_live = (n_live + 7) >> 3;
+  const int x = id & 7, j = id >> 3;
+  const int t = x * per_xcd_live + j;               // compacted task index: XCD-contiguous like the full pass
+  if (j < per_xcd_live && t < n_live) {
+    const int k = t / per_b;
+    const int task = nth_sample(live, k, lane) * per_b + (t - k * per_b);
+    if (student) march_body<true, false, false, false, false, false, false, kSpecStudentNoEpi>(&pk->stu, task);
+    else march_body<false, false, false, false, false, false, false>(&pk->ens, task);
+    return;
+  }
+  if (!student) return;  // nothing reads a dead sample's ensemble map
+  // surplus workgroups, numbered 0 .. per_xcd * 8 - n_live - 1; the first ones take a dead task each
+  const int s = j >= per_xcd_live ? (j - per_xcd_live) * 8 + x : (kp->per_xcd - per_xcd_live) * 8 + (t - n_live);
+  const unsigned long long dead = ~live & all;
+  if (s >= __popcll(dead) * per_b) return;
+  const int k = s / per_b;
+  march_zero_task(&pk->stu, nth_sample(dead, k, lane) * per_b + (s - k * per_b));
 }
 
 #ifdef MAL_EXPERIMENTS  // option "march3" (measured slower, LABBOOK.md 6): not in the default build
@@ -1736,6 +1819,39 @@ int march_launch(MarchParams& p, int flags, hipStream_t st) {
   return launch_status();
 }
 
+// whether the options and the shape let the two forked passes of a --temporal step run as march_pair_kernel: both
+// instantiations it holds are the ones march_launch would pick (generic forward pass, kSpecStudentNoEpi)
+bool march_pair_qualifies(int B, int H, int W) {
+  return g_march_lean && g_debug == 0 && B <= 64 && (long long)H * W * (kTexel * 4) < (1ll << 24);
+}
+// the ensemble pass (`ens` nullable: --no_ens) and the student's pass without epilogue as one launch over the tasks of the
+// samples whose scale (stu.sample_scale, read on the device) is not zero; stu_first: the student's tasks take the leading workgroups
+int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStream_t st) {
+  auto prep = [&](MarchParams& p, int flags) {
+    march_decompose(p, flags);
+    p.debug = g_debug; p.flip_odd = g_march_flip; p.packed = 3;
+  };
+  auto plain = [](const MarchParams& p) {  // nothing of the other formulations' operands
+    return p.cam && p.cam_ready && !p.dbg && !p.depth_out && !p.avg && !p.no_ssim && !p.framed && !p.forced_w && !p.color_out[0] &&
+           !p.region && p.block_sums && p.convention == 0;
+  };
+  prep(stu, MAL_F_GRAD);
+  if (ens) prep(*ens, 0);
+  if (!march_pair_qualifies(stu.B, stu.H, stu.W) || !plain(stu) || (ens && !plain(*ens))) return MAL_EINVAL;
+  if (stu.disp2 || !stu.ext_mask || !stu.lowest_cost || !stu.mono_disp || !stu.sample_scale || !stu.g_reproj || stu.cmask_out ||
+      stu.min_reproj2 || stu.mono_reproj)
+    return MAL_EINVAL;
+  if (ens && (ens->B != stu.B || ens->H != stu.H || ens->W != stu.W || ens->sample_scale || ens->g_reproj)) return MAL_EINVAL;
+  MarchPairParams pk;
+  pk.stu = stu;
+  pk.ens = ens ? *ens : stu;  // (no workgroup reads it when ens_blocks == 0)
+  pk.ens_blocks = ens ? ens->per_xcd * 8 : 0;
+  pk.stu_blocks = stu.per_xcd * 8;
+  pk.stu_first = stu_first ? 1 : 0;
+  hipLaunchKernelGGL(march_pair_kernel, dim3((unsigned)(pk.ens_blocks + pk.stu_blocks)), dim3(64), 0, st, pk);
+  return launch_status();
+}
+
 int pack_identity_tasks_per_sample(int H, int W) { return ((W + 61) / 62) * ((H + g_pack_rows - 1) / g_pack_rows); }
 
 int pack_identity_launch(const float* target, const float* src0, const float* src1, int B, int H, int W,
@@ -1916,7 +2032,7 @@ extern "C" int mal_set_option(const char* name, int value) {
   if (eq("costvol_impl")) { if (value < 0 || value > 1) return MAL_EINVAL; g_costvol_impl = value; return MAL_OK; }
   if (eq("step_overlap")) { if (value < 0 || value > 2) return MAL_EINVAL; g_step_overlap = value; return MAL_OK; }
   if (eq("march_halo1")) { g_march_halo1 = value != 0; return MAL_OK; }
-  if (eq("student_overlap")) { g_student_overlap = value != 0; return MAL_OK; }
+  if (eq("student_overlap")) { if (value < 0 || value > 2) return MAL_EINVAL; g_student_overlap = value; return MAL_OK; }
   if (eq("ms_fold")) { g_ms_fold = value != 0; return MAL_OK; }
   if (eq("sweeps_batched")) { g_sweeps_batched = value != 0; return MAL_OK; }
   if (eq("tail_overlap")) { g_tail_overlap = value != 0; return MAL_OK; }

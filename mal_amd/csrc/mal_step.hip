@@ -111,6 +111,7 @@ static StepWs carve_step(void* base, int B, int H, int W) {
 struct EpiParams {
   const float *disp_s, *disp_t, *mono_reproj, *ens_reproj, *multi_reproj, *ext_mask, *lowest_cost, *sample_scale, *ens_disp;
   int scale_is_mask, dual;
+  int skip_dead;  // the marching passes skipped the samples whose scale is 0 (aug_skip_applies): their minima were never written
   float min_disp, range, merge_cons, merge_distil;
   float *G_c, *G_e; double* partials; unsigned* dbg; int B, HW;
 };
@@ -166,7 +167,35 @@ MAL_DEV void step_epilogue_block(const EpiParams& p, int bid) {
   auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
   const bool aligned = al16(p.ext_mask) && al16(p.disp_t) && al16(p.lowest_cost) && al16(p.multi_reproj) && al16(p.disp_s) &&
                        al16(p.mono_reproj) && al16(p.ens_reproj) && al16(p.ens_disp) && al16(p.G_c) && al16(p.G_e);
-  if (((per | p.HW) & 3) == 0 && aligned) {
+  if (p.skip_dead && sscale == 0.0f) {
+    // A dead sample: its weight is an exact zero at every pixel, so cm = 1, mm = 0 -- only the consistency term and its
+    // gradient are left, pointwise in the two disparities.  Same expressions and accumulation positions as one() (the
+    // distillation sum would receive + 0.0f, the merged gradient merge_distil * (+-0)); none of the three per-pixel minima,
+    // the cost map or the consistency mask is loaded: the skipped tasks never wrote the first two.
+    auto dead_one = [&](float dt, float ds) __attribute__((always_inline)) {
+      const float dmono = depth_of(dt, p.min_disp, p.range);
+      const float dm = depth_of(ds, p.min_disp, p.range);
+      const float ddepth = -(dm * dm) * p.range;
+      const float cm = 1.0f;
+      const float dc = dm - dmono;
+      acc_cons += fabsf(dc) * cm;
+      const float gc = sgnf(dc) * cm * ddepth;
+      return fma_(p.merge_cons, gc, 0.0f);
+    };
+    if (((per | p.HW) & 3) == 0 && al16(p.disp_t) && al16(p.disp_s) && al16(p.G_c)) {
+      typedef float v4 __attribute__((ext_vector_type(4)));
+      for (int i0 = lo + tid * 4; i0 < hi; i0 += 1024) {
+        const size_t i = base + i0;
+        const v4 dt = *reinterpret_cast<const v4*>(p.disp_t + i), ds = *reinterpret_cast<const v4*>(p.disp_s + i);
+        v4 gc;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gc[k] = dead_one(dt[k], ds[k]);
+        *reinterpret_cast<v4*>(p.G_c + i) = gc;
+      }
+    } else {
+      for (int i0 = lo + tid; i0 < hi; i0 += 256) p.G_c[base + i0] = dead_one(p.disp_t[base + i0], p.disp_s[base + i0]);
+    }
+  } else if (((per | p.HW) & 3) == 0 && aligned) {
     // four consecutive pixels per thread, 16-byte accesses (every map's sample and every block's range start 16-byte aligned)
     typedef float v4 __attribute__((ext_vector_type(4)));
     for (int i0 = lo + tid * 4; i0 < hi; i0 += 1024) {
@@ -601,20 +630,24 @@ static int launch_teacher(const mal_step_args* a, const StepWs& w, float* mono_r
 }
 
 // the ensemble pass (no gradient): the averaged disparity is formed inside the kernel (trainer.py:594-600)
-static int launch_ensemble(const mal_step_args* a, const StepWs& w, float* ens_reproj, hipStream_t st) {
+static MarchParams ensemble_params(const mal_step_args* a, const StepWs& w, float* ens_reproj) {
   MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, 0);
   p.disp = a->disp_teacher; p.disp2 = a->disp_student; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
   if (a->ens_disp) { p.disp = a->ens_disp; p.disp2 = nullptr; }  // --learn_ens: the head's disparity (trainer.py:596-597)
   p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
   p.min_reproj = ens_reproj; p.block_sums = w.bs_e; p.block_gP = w.bgP_e;
   p.cam = w.cam; p.cam_ready = 1;
+  return p;
+}
+static int launch_ensemble(const mal_step_args* a, const StepWs& w, float* ens_reproj, hipStream_t st) {
+  MarchParams p = ensemble_params(a, w, ens_reproj);
   return march_launch(p, MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
 }
 
 // the student's pass (trainer.py:592-612): with `epi` the consistency / distillation epilogue rides in it (the step without the
 // temporal hint); without, it leaves its per-pixel min in multi_reproj and the final launch forms those terms later
-static int launch_student(const mal_step_args* a, const StepWs& w, float* mono_reproj, float* ens_reproj, float* multi_reproj,
-                          bool epi, hipStream_t st, int* per_sample) {
+static MarchParams student_params(const mal_step_args* a, const StepWs& w, float* mono_reproj, float* ens_reproj, float* multi_reproj,
+                                  bool epi) {
   const int B = a->B, H = a->H, W = a->W;
   MarchParams p = march_params(B, H, W, a->min_depth, a->max_depth, 1e-7f, 0);
   p.disp = a->disp_student; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
@@ -634,6 +667,11 @@ static int launch_student(const mal_step_args* a, const StepWs& w, float* mono_r
   p.bnd = g_march_halo1 ? w.bnd_s : nullptr;
   p.cam = w.cam; p.cam_ready = 1;
   p.dbg = a->dec_student;
+  return p;
+}
+static int launch_student(const mal_step_args* a, const StepWs& w, float* mono_reproj, float* ens_reproj, float* multi_reproj,
+                          bool epi, hipStream_t st, int* per_sample) {
+  MarchParams p = student_params(a, w, mono_reproj, ens_reproj, multi_reproj, epi);
   int rc = march_launch(p, MAL_F_GRAD | (epi ? MAL_F_EPILOGUE : 0) | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
   if (per_sample) *per_sample = p.strips * p.segs;
   return rc;
@@ -667,6 +705,7 @@ static int launch_student_temporal(const mal_step_args* a, const StepWs& w, hipS
   p.dbg = a->dec_student;
   return march_launch(p, MAL_F_GRAD | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
 }
+static bool aug_skip_applies(const mal_step_args* a);
 static EpiParams epilogue_params(const mal_step_args* a, const StepWs& w, const float* mono_reproj, const float* ens_reproj,
                                  const float* multi_reproj) {
   const int B = a->B, H = a->H, W = a->W;
@@ -676,6 +715,7 @@ static EpiParams epilogue_params(const mal_step_args* a, const StepWs& w, const 
   e.multi_reproj = multi_reproj; e.ext_mask = a->consistency_mask; e.lowest_cost = a->lowest_cost;
   e.sample_scale = a->augmentation_keep; e.scale_is_mask = (a->flags & MAL_STEP_AUG_MASK) ? 1 : 0;
   e.ens_disp = a->ens_disp; e.dual = (a->flags & MAL_STEP_DUAL_DISTIL) ? 1 : 0;
+  e.skip_dead = aug_skip_applies(a) ? 1 : 0;
   e.min_disp = mp.min_disp; e.range = mp.range;
   e.merge_cons = (float)((double)a->w_main / ((double)B * H * W)); e.merge_distil = (float)((double)a->w_distil / ((double)B * H * W));
   e.G_c = w.G_c; e.G_e = (a->ens_disp || e.dual) ? w.G_e : nullptr; e.partials = w.bs_d; e.dbg = a->dec_student; e.B = B; e.HW = H * W;
@@ -788,8 +828,9 @@ int side_end(hipStream_t st) {
 int side_wait(hipStream_t st, bool always) { return join_side(st, always); }
 }
 // what is forked beside the producer: the ensemble pass (unless --no_ens) and, with option "student_overlap" (default), the
-// student's marching pass without its epilogue
-namespace mal { opt_t g_student_overlap{1}; opt_t g_side_order{0}; }
+// student's marching pass without its epilogue; value 2 (default): the two as ONE launch that skips the augmented samples
+// (aug_skip_applies), 1: a launch each, every sample computed
+namespace mal { opt_t g_student_overlap{2}; opt_t g_side_order{0}; }
 // option "tail_overlap": 1 = a --temporal step's backward chain (producer's backward -> teacher's gradient sweep) runs on the
 // library's side stream behind the FUSED SWEEP only, beside the epilogue and the reduction of the forward (in a captured graph
 // the two chains are independent; eager: the same order as before, the side stream simply has nothing to wait for)
@@ -837,6 +878,23 @@ static bool student_warp_forked(const mal_step_args* a) {
   return side_forked(a) && g_step_overlap == 1 && (a->flags & MAL_STEP_TEMPORAL) && (a->flags & MAL_STEP_MAIN_TEMPORAL);
 }
 
+// Augmented samples (networks/repdepth.py:277-295 marks about half of them) carry the weight 1 - augmentation_mask = 0 in the
+// student's masked reprojection term and in the distillation term (loss_utils.py:192-199,253), and the ensemble's reprojection
+// is read by the distillation argmin only (:237-245): for such a sample the ensemble pass and the student's marching pass
+// compute nothing but exact zeros.  When the step hands no per-pixel map or decision plane of the two passes to the caller,
+// they go out as one launch over the other samples' tasks (march_pair_launch) and the epilogue takes its dead-sample path.
+// Everything the predicate reads is in the argument block and the options, so _warp and _fwd agree on it.
+static bool aug_skip_applies(const mal_step_args* a) {
+  return g_student_overlap == 2 && (a->flags & MAL_STEP_TEMPORAL) && !(a->flags & (MAL_STEP_MAIN_TEMPORAL | MAL_STEP_DUAL_DISTIL)) &&
+         student_forked(a) && !a->ens_disp && a->augmentation_keep && !a->multi_reproj && !a->ens_reproj &&
+         !a->consistency_mask_out && !a->dec_student && march_pair_qualifies(a->B, a->H, a->W);
+}
+static int launch_forked_pair(const mal_step_args* a, const StepWs& w, hipStream_t st) {
+  MarchParams stu = student_params(a, w, nullptr, nullptr, w.multi_reproj, false);
+  MarchParams ens = ensemble_params(a, w, w.ens_reproj);
+  return march_pair_launch(ensemble_forked(a) ? &ens : nullptr, stu, g_side_order ? 1 : 0, st);
+}
+
 static int fork_ensemble(const mal_step_args* a, const StepWs& w, hipStream_t st) {
   SideStream* ss = side_stream(st);
   if (!ss) return MAL_ELAUNCH;
@@ -848,6 +906,12 @@ static int fork_ensemble(const mal_step_args* a, const StepWs& w, hipStream_t st
   }
   // option "side_order" 1: the student's pass first, the (lighter, forward-only) ensemble pass behind it -- the one that ends up
   // beside the fused sweep; 0: ensemble first
+  if (aug_skip_applies(a)) {  // both forked passes in one launch, augmented samples skipped
+    rc = launch_forked_pair(a, w, ss->s);
+    if (hipEventRecord(ss->join, ss->s) != hipSuccess) return rc ? rc : MAL_ELAUNCH;
+    ss->pending = true;
+    return rc;
+  }
   if (g_side_order && student_forked(a))
     rc = launch_student(a, w, nullptr, nullptr, a->multi_reproj ? a->multi_reproj : w.multi_reproj, false, ss->s, nullptr);
   if (!rc && ensemble_forked(a)) rc = launch_ensemble(a, w, a->ens_reproj ? a->ens_reproj : w.ens_reproj, ss->s);
