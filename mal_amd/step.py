@@ -534,6 +534,8 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
                 torch.randn((B, 1, H, W))  # compute_main_losses' dead draw (loss_utils.py:178)
     aug = outputs["augmentation_mask"][:opt.batch_size]
     aug_is_mask = aug.dtype == torch.float32 and aug.is_contiguous()  # then 1 - mask is formed on the device
+    if not aug_is_mask and not aug.is_floating_point():
+        aug = aug.to(torch.float32)  # (a bool mask: torch refuses 1 - mask)
     keep = aug.reshape(B) if aug_is_mask else (1 - aug).to(torch.float32).reshape(B)
     blc = bool(getattr(opt, "loss_blc", False))
     w_main, w_distil = 1.0, 1.0
@@ -768,6 +770,8 @@ def loss_step_multiscale(opt, inputs, mono_outputs, outputs, noises=None, want_m
                     torch.randn((B, 1, H, W))  # the student's dead draws (trainer.py:1305-1308,1325)
     aug = outputs["augmentation_mask"][:opt.batch_size]
     aug_is_mask = aug.dtype == torch.float32 and aug.is_contiguous()
+    if not aug_is_mask and not aug.is_floating_point():
+        aug = aug.to(torch.float32)  # (a bool mask: torch refuses 1 - mask)
     keep = aug.reshape(B) if aug_is_mask else (1 - aug).to(torch.float32).reshape(B)
     consts = ((color0, inputs[("color", -1, 0)], inputs[("color", 1, 0)]), [inputs[("color", 0, s)] for s in range(1, sclm + 1)],
               inputs[("K", 0)], inputs[("inv_K", 0)], outputs["consistency_mask"].to(torch.float32), keep,

@@ -186,16 +186,11 @@ def test_the_device_decides_at_replay():
     torch.cuda.current_stream().wait_stream(s_)
 
 
-def test_against_the_oracle():
-    """the golden --temporal fixture with the first sample augmented, no maps requested (the skip applies), against the CPU
-    oracle with the gates tests/test_gpu_parity.py::_check_case (test_step_parity) puts on this fixture's scalars and
+def check_against_the_oracle(b, kw, n0, n1):
+    """a --temporal step on `b` (its augmentation mask as given), no maps requested (the skip applies), against the CPU
+    oracle with the gates tests/test_gpu_parity.py::_check_case (test_step_parity) puts on a fixture's scalars and
     gradients; the maps that test reads from the kernels are not returned here, the near-tie sets are the oracle's"""
-    z = G.load("step_b2_32x64_temporal")
-    b = G.batch_from_golden(z)
     B, _, H, W = b["color0"].shape
-    b["augmentation_mask"] = torch.tensor([1.0, 0.0]).reshape(b["augmentation_mask"].shape)
-    n0, n1 = G.noises(z, (B, 1, H, W))
-    kw = G.opt_kwargs(z)
     assert kw.get("temporal") and not kw.get("main_temporal") and "syn_rects" in b
     o = HH.run_oracle(b, kw, n0, n1)
     from mal_amd import config
@@ -256,6 +251,16 @@ def test_against_the_oracle():
         extra = 0.0 if key == "disp_student" else renorm
         print(key, l2rel(g, ref), floor)
         assert l2rel(g, ref) <= max(1e-4, 1.5 * floor) + extra, (key, l2rel(g, ref), floor)
+
+
+def test_against_the_oracle():
+    """the golden --temporal fixture with the first sample augmented"""
+    z = G.load("step_b2_32x64_temporal")
+    b = G.batch_from_golden(z)
+    B, _, H, W = b["color0"].shape
+    b["augmentation_mask"] = torch.tensor([1.0, 0.0]).reshape(b["augmentation_mask"].shape)
+    n0, n1 = G.noises(z, (B, 1, H, W))
+    check_against_the_oracle(b, G.opt_kwargs(z), n0, n1)
 
 
 @pytest.mark.parametrize("case", ["want_maps", "decisions", "main_temporal", "dual_distil", "learn_ens"])
