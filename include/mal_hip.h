@@ -577,6 +577,18 @@ int mal_dr_loss_bwd(const mal_dr_args* args);
 int mal_upsample_bilinear(const float* x, int B, int h, int w, int H, int W, float* out, void* stream);
 int mal_upsample_bilinear_adjoint(const float* g_out, int B, int h, int w, int H, int W, float* g_x, void* stream);
 
+/* ---- the glue between two convolutions of the depth decoder (mal_amd/networks.py DepthDecoder) as ONE pass each way:
+ * F.pad(cat([interpolate(F.elu(x), scale_factor=up, mode="nearest"), skip], 1), (1,1,1,1), mode="reflect") and its adjoint.
+ * x (B,C,h,w); skip (B,Cs,up*h,up*w), nullable when Cs = 0; out and g_out (B,C+Cs,up*h+2,up*w+2).  up in {1,2}, elu in
+ * {0,1} (0: no activation).  The adjoint is a gather in a fixed order (mal_amd/csrc/mal_glue.hip states it; no atomics,
+ * no zero fill); it reads x only with elu = 1 (a' = x > 0 ? 1 : expm1f(x) + 1), and a NULL gx or gskip is not computed.
+ * MAL_EINVAL: a null required pointer, up/elu out of range, B, C, h or w < 1, Cs < 0, Cs > 0 without skip, up*h < 2 or
+ * up*w < 2 (reflection needs two rows), or a padded tensor of 2^31 elements or more (32-bit indices). */
+int mal_decoder_join_fwd(const float* x, const float* skip, float* out, int B, int C, int Cs, int h, int w, int up, int elu,
+                         void* stream);
+int mal_decoder_join_bwd(const float* g_out, const float* x, float* gx, float* gskip, int B, int C, int Cs, int h, int w,
+                         int up, int elu, void* stream);
+
 /* ---- N2: the temporal-hint producer's per-sample arithmetic, manydepth/dyn_utils.py:6-119 --------
  * (fill_dynamic_obj + generate_dynamic_instance), given the matched instance masks of the two warped frames
  * (num,H,W as bytes, non-zero = set; Mask2Former stays outside, the matcher is mal_match below).  Per instance the displacement

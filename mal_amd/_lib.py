@@ -104,6 +104,8 @@ SIGNATURES = {
     "mal_dr_loss_bwd": (i32, [vp]),
     "mal_upsample_bilinear": (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, vp]),
     "mal_upsample_bilinear_adjoint": (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, vp]),
+    "mal_decoder_join_fwd": (i32, [c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "mal_decoder_join_bwd": (i32, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mal_set_option": (i32, [C.c_char_p, i32]),
     "mal_get_option": (i32, [C.c_char_p, C.POINTER(i32)]),
     "mal_build_has_experiments": (i32, []),

@@ -204,9 +204,12 @@ class ConvBlock(nn.Module):
 class DepthDecoder(nn.Module):
     """depth_decoder.py:16-68: ``("disp", 0)`` only, whatever ``scales`` says."""
 
-    def __init__(self, num_ch_enc, scales=range(4), num_output_channels=1, use_skips=True):
+    def __init__(self, num_ch_enc, scales=range(4), num_output_channels=1, use_skips=True, fused_glue=False):
         super().__init__()
         self.num_output_channels, self.use_skips, self.scales = num_output_channels, use_skips, scales
+        # read at forward time: the ELU / x2 upsampling / concatenation / reflection padding between two convolutions as one
+        # HIP pass each way (mal_amd.glue.decoder_join) instead of four ATen ones; same modules, same state dict
+        self.fused_glue = fused_glue
         self.num_ch_enc = num_ch_enc
         self.num_ch_dec = np.array([16, 32, 64, 128, 256])
         self.convs = OrderedDict()
@@ -221,7 +224,23 @@ class DepthDecoder(nn.Module):
         self.decoder = nn.ModuleList(list(self.convs.values()))
         self.sigmoid = nn.Sigmoid()
 
+    def _forward_fused(self, input_features):
+        """the same function with every padded convolution input written by one decoder_join: the activation of a ConvBlock
+        moves in front of the next convolution, whose nn.Conv2d is called on the padded tensor directly"""
+        from .glue import decoder_join
+        x = input_features[-1]
+        for i in range(4, -1, -1):
+            if i == 4:  # the encoder's last map enters without an activation: one ATen pad against one join, nothing to fuse,
+                x = self.convs[("upconv", i, 0)].conv(x)  # and at 6x20 the join measured slower (DESIGN.md 12): ATen stays
+            else:
+                x = self.convs[("upconv", i, 0)].conv.conv(decoder_join(x, None, up=1, elu=True))
+            skip = input_features[i - 1] if self.use_skips and i > 0 else None
+            x = self.convs[("upconv", i, 1)].conv.conv(decoder_join(x, skip, up=2, elu=True))
+        return {("disp", 0): self.sigmoid(self.convs[("dispconv", 0)].conv(decoder_join(x, None, up=1, elu=True)))}
+
     def forward(self, input_features):
+        if self.fused_glue:
+            return self._forward_fused(input_features)
         outputs = {}
         x = input_features[-1]
         for i in range(4, -1, -1):
@@ -277,9 +296,9 @@ class RepDepth(nn.Module):
                                              min_depth_bin=0.1, max_depth_bin=20.0,
                                              depth_binning=g("depth_binning", "linear"),
                                              num_depth_bins=g("num_depth_bins", 96))
-        self.depth = DepthDecoder(self.encoder.num_ch_enc, g("scales", [0]))
+        self.depth = DepthDecoder(self.encoder.num_ch_enc, g("scales", [0]), fused_glue=g("fused_decoder", False))
         self.mono_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained")
-        self.mono_depth = DepthDecoder(self.mono_encoder.num_ch_enc, g("scales", [0]))
+        self.mono_depth = DepthDecoder(self.mono_encoder.num_ch_enc, g("scales", [0]), fused_glue=g("fused_decoder", False))
         self.pose_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", num_input_images=2)
         self.pose = PoseDecoder(self.pose_encoder.num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
         self.matching_ids = [0]
