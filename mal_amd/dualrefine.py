@@ -13,7 +13,9 @@ shipped file carries (:452-455,481-484) are not behaviour and are not reproduced
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from types import SimpleNamespace
+from typing import Any, NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -29,6 +31,7 @@ from . import functional as Fn
 from . import layers
 from . import loss_utils
 from . import ops
+from . import step
 from .trainer import WarpContext
 
 
@@ -48,18 +51,29 @@ def default_options(**kw):
     return SimpleNamespace(**o)
 
 
-_DR_WS = {}
+# DrLossStepFn's ``consts`` / ``cfg``: tuples in the positional order the function has always read (mal_amd.step has the others)
+class DrConsts(NamedTuple):
+    color0: Any; color_m1: Any; color_p1: Any; K: Any; inv_K: Any
+    cmask: Any; noises: Any  # nullable; one (B,1,H,W) map per iteration, or None
+    color0_s: Any = None     # inputs[("color", 0, scale)] of a scale > 0
 
 
-def _dr_workspace(dev, B, H, W, n, slot=0):
-    """``slot``: the scale of opt.scales the call belongs to -- every scale's call keeps its own maps until its backward"""
-    need = L.load().mal_dr_workspace_bytes(B, H, W, n)
-    from . import step as _step
-    key = (dev.index, ops._stream(), B, H, W, n, slot, _step._WS_SLOT)  # (step.workspace_slot: see there)
-    ws = _DR_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _DR_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
+class DrCfg(NamedTuple):
+    min_depth: float; max_depth: float; smooth_weight: float
+    flags: int; n: int; philox: Any  # MAL_DR_*; deq iterations of the call; None, or the seed
+    scale: int = 0; texels_from: Any = None  # the workspace of the step's first call (texels + identity term)
+    want_decisions: bool = False  # parity instrumentation (tests): decision planes per iteration
+    pose_update: Any = None       # the pose-update losses: {"noise": (B,1,H,W) N(0,1) or None, "into": see forward}
+
+
+DrKept = namedtuple("DrKept", "tens cons cm nz ws losses total pu_total pu_nz")  # ctx.keep: what the C struct points to
+
+
+class VDR:
+    """slots of DualRefine's loss vector (include/mal_hip.h:496-497,504): four terms per iteration, then the call's sums"""
+    REPROJ, CONSISTENCY, SMOOTH, RUNNING = range(4)  # + 4 * iteration
+    SIZE = 4 * L.DR_MAX_ITERS + 4
+    TOTAL, FINAL_RUNNING, POSE_UPDATE = 4 * L.DR_MAX_ITERS, 4 * L.DR_MAX_ITERS + 1, 4 * L.DR_MAX_ITERS + 2
 
 
 class DrLossStepFn(Function):
@@ -67,20 +81,16 @@ class DrLossStepFn(Function):
     per direction (``mal_dr_loss_fwd/_bwd``).  Leaves: ``disp[it]`` (n of them, at the scale's own size), then ``T_m1[it]``,
     then ``T_p1[it]`` ((B,4,4) each; a pose the trainer detaches simply arrives without ``requires_grad``).  For a scale > 0
     the disparities are upsampled here (trainer.py:411-412) and the adjoint is applied to what the library hands back.
-    ``cfg[9]`` (a dict, scale 0 only): the pose-update losses (trainer.py:457-480,699-767) ride on the call as one more marching
+    ``cfg.pose_update`` (a dict, scale 0 only): the pose-update losses (trainer.py:457-480,699-767) ride on the call as one more marching
     pass -- four more leaves follow: the disparity paired with the refined pose for frame -1, iteration 0's disparity (frame
     +1's candidate is ("color", 1, 0, 0)), ("cam_T_cam", 0, -1, 1), ("cam_T_cam", 0, 1); the term is the SECOND output (its own
     cotangent: upstream adds it after the division by len(scales))."""
 
     @staticmethod
     def forward(ctx, consts, cfg, *leaves):
-        color0, color_m1, color_p1, K, inv_K, cmask, noises = consts[:7]
-        color0_s = consts[7] if len(consts) > 7 else None
-        min_depth, max_depth, smooth_weight, flags, n, philox = cfg[:6]
-        scale = cfg[6] if len(cfg) > 6 else 0
-        texels_from = cfg[7] if len(cfg) > 7 else None  # the workspace of the step's first call (texels + identity term)
-        want_dec = len(cfg) > 8 and cfg[8]               # parity instrumentation (tests): decision planes per iteration
-        pu = cfg[9] if len(cfg) > 9 else None            # the pose-update losses: {"noise": (B,1,H,W) N(0,1) or None}
+        consts, cfg = DrConsts(*consts), DrCfg(*cfg)
+        color0, color_m1, color_p1, K, inv_K, cmask, noises, color0_s = consts
+        min_depth, max_depth, smooth_weight, flags, n, philox, scale, texels_from, want_dec, pu = cfg
         if noises is not None and len(noises) != n:
             raise L.MalError("DrLossStepFn: one noise map per iteration (%d), or None; got %d" % (n, len(noises)))
         req, p = ops._req, ops._p
@@ -107,11 +117,9 @@ class DrLossStepFn(Function):
             a.noise[it] = p(nz[it])
         a.consistency_mask = p(cm)
         if philox is not None:  # drawn in the step's first launch; the device counter advances with every (replayed) step
-            from . import step as _step
-            ctr = _step.noise_counter(dev)
             a.flags |= L.DR_NOISE_PHILOX
-            a.noise_seed, a.noise_counter = int(philox) & 0xFFFFFFFFFFFFFFFF, ctr.data_ptr()
-        losses = torch.empty(4 * L.DR_MAX_ITERS + 4, dtype=torch.float32, device=dev)
+            a.noise_seed, a.noise_counter = int(philox) & 0xFFFFFFFFFFFFFFFF, step.noise_counter(dev).data_ptr()
+        losses = torch.empty(VDR.SIZE, dtype=torch.float32, device=dev)
         total = torch.empty(1, dtype=torch.float32, device=dev)
         a.losses, a.loss_total = p(losses), p(total)
         pu_total, pu_nz = None, None
@@ -133,7 +141,8 @@ class DrLossStepFn(Function):
             a.pu_disp_m1, a.pu_disp_p1, a.pu_T_m1, a.pu_T_p1 = (p(t) for t in ops_)
             a.pu_disp_m1_into, a.pu_disp_p1_into, a.pu_T_m1_into, a.pu_T_p1_into = (0 if i is None else i + 1 for i in into)
             a.pu_noise, a.pu_loss_total = p(pu_nz), p(pu_total)
-        ws = _dr_workspace(dev, B, H, W, n, slot=int(scale))
+        # (keyed by the scale too: every scale's call of a step keeps its own maps until its backward)
+        ws = step.byte_workspace("dualrefine", dev, L.load().mal_dr_workspace_bytes(B, H, W, n), B, H, W, n, int(scale))
         a.ws, a.ws_bytes, a.stream = p(ws), ws.numel(), ops._stream()
         if texels_from is not None:
             a.texels_from = p(texels_from)
@@ -146,7 +155,7 @@ class DrLossStepFn(Function):
                 decs.append(torch.zeros((L.DEC_PLANES, B, H, W), dtype=torch.int32, device=dev))
                 a.pu_dec = p(decs[-1])
         L.check(L.load().mal_dr_loss_fwd(C.byref(a)), "mal_dr_loss_fwd")
-        ctx.args, ctx.keep, ctx.n, ctx.scale, ctx.up = a, (tens, cons, cm, nz, ws, losses, total, pu_total, pu_nz), n, int(scale), up
+        ctx.args, ctx.keep, ctx.n, ctx.scale, ctx.up = a, DrKept(tens, cons, cm, nz, ws, losses, total, pu_total, pu_nz), n, int(scale), up
         ctx.pu = pu is not None
         ctx.texels_from = texels_from  # (kept alive: the passes of this call read it)
         ctx.ws_token = ops.claim_workspace(ws)
@@ -157,10 +166,10 @@ class DrLossStepFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_total, g_pu=None, _g_losses=None, _g_ws=None, *_g_decs):
-        n, tens = ctx.n, ctx.keep[0]
+        n, tens = ctx.n, ctx.keep.tens
         if g_total is None and (g_pu is None or not ctx.pu):
             return (None,) * (2 + len(tens))
-        ops.check_workspace(ctx.keep[4], ctx.ws_token, "DualRefineLossPath.loss_step backward")
+        ops.check_workspace(ctx.keep.ws, ctx.ws_token, "DualRefineLossPath.loss_step backward")
         zero = lambda g: torch.zeros(1, dtype=torch.float32, device=tens[0].device) if g is None else g.reshape(1).contiguous()
         g_total = zero(g_total)
         a = ctx.args
@@ -226,15 +235,15 @@ class DualRefineLossPath:
                 Ts = [self._pose_for(outputs, f, deq_iter) for f in fids]
                 K, inv_K = inputs[("K", 0)], inputs[("inv_K", 0)]
                 srcs = [inputs[("color", f, 0)] for f in fids]
-                cfg = (float(opt.min_depth), float(opt.max_depth), 1e-7, self.convention)
+                min_depth, max_depth, eps = float(opt.min_depth), float(opt.max_depth), 1e-7
                 if self.fuse and not opt.avg_reprojection and not opt.no_ssim:
                     _, depth = layers.disp_to_depth(disp, opt.min_depth, opt.max_depth)
                     outputs[("depth", 0, scale, deq_iter)] = depth
                     outputs[("mal_ctx", scale, deq_iter)] = WarpContext(
-                        disp=disp, T=Ts, K=K, inv_K=inv_K, min_depth=cfg[0], max_depth=cfg[1], eps=cfg[2],
-                        convention=cfg[3], srcs=srcs, fids=fids)
+                        disp=disp, T=Ts, K=K, inv_K=inv_K, min_depth=min_depth, max_depth=max_depth, eps=eps,
+                        convention=self.convention, srcs=srcs, fids=fids)
                 else:
-                    res = Fn.WarpFn.apply(disp, K, inv_K, cfg, len(fids), *Ts, *srcs)
+                    res = Fn.WarpFn.apply(disp, K, inv_K, (min_depth, max_depth, eps, self.convention), len(fids), *Ts, *srcs)
                     outputs[("depth", 0, scale, deq_iter)] = res[0]
                     for i, f in enumerate(fids):
                         outputs[("sample", f, scale, deq_iter)] = res[1 + i]
@@ -383,11 +392,8 @@ class DualRefineLossPath:
                 (L.DR_AVG if opt.avg_reprojection else 0) | (L.DR_NO_SSIM if opt.no_ssim else 0)
         units = [(s_, it) for s_ in scales if s_ != 1 for it in range(n_full if s_ in (0, 1, 2) else 1)]
         philox = None
-        if noises is None and not opt.disable_automasking:
-            if config.noise_source == "philox":  # drawn inside each call's first launch: no RNG launch, no host work
-                philox = config.noise_seed
-            else:
-                noises = [loss_utils.draw_noise((B, 1, H, W), target.device) for _ in units]  # one draw per visit (:586-587)
+        if noises is None and not opt.disable_automasking:  # one draw per visit (:586-587), no dead ones
+            noises, philox = step.draw_noise_maps((B, 1, H, W), target.device, len(units), 0)
         if noises is not None and len(noises) != len(units):
             raise L.MalError("loss_step: `noises` holds one map per visited (scale, iteration), %d here %s; got %d"
                              % (len(units), units, len(noises)))
@@ -412,8 +418,8 @@ class DualRefineLossPath:
                 cmask = outputs["consistency_mask"].to(torch.float32)
             nz = None if noises is None else list(noises[k:k + n])
             k += n
-            consts = (target, inputs[("color", -1, 0)], inputs[("color", 1, 0)], inputs[("K", 0)], inputs[("inv_K", 0)], cmask, nz,
-                      inputs[("color", 0, scale)] if scale else None)
+            consts = DrConsts(target, inputs[("color", -1, 0)], inputs[("color", 1, 0)], inputs[("K", 0)], inputs[("inv_K", 0)],
+                              cmask, nz, inputs[("color", 0, scale)] if scale else None)
             pu, pu_leaves = None, ()
             if pose_update and scale == 0:
                 # frame -1: the refined pose paired with the last iteration's depth -- or iteration 0's, detached (:463-469);
@@ -432,8 +438,8 @@ class DualRefineLossPath:
                     if hit:
                         pu_leaves[j] = None
                 pu = {"noise": None if opt.disable_automasking else pose_noise, "into": tuple(into)}
-            cfg = (opt.min_depth, opt.max_depth, opt.disparity_smoothness / (2 ** scale), flags, n, philox, scale, first_ws,
-                   bool(want_decisions), pu)
+            cfg = DrCfg(opt.min_depth, opt.max_depth, opt.disparity_smoothness / (2 ** scale), flags, n, philox, scale, first_ws,
+                        bool(want_decisions), pu)
             tot_s, pu_s, v, ws_s, *decs_s = DrLossStepFn.apply(consts, cfg, *disps, *T_m1, *T_p1, *pu_leaves)
             for it, d in enumerate(decs_s):
                 decisions[(scale, it) if it < n else ("pose", 0)] = d
@@ -442,11 +448,11 @@ class DualRefineLossPath:
             if first_ws is None:
                 first_ws = ws_s
             total = tot_s.reshape(()) if total is None else total + tot_s.reshape(())
-            losses["reproj_loss/%d" % scale] = v[4 * (n - 1)]
+            losses["reproj_loss/%d" % scale] = v[4 * (n - 1) + VDR.REPROJ]
             for it in range(n):
-                losses["loss/%d_%d" % (scale, it)] = v[4 * L.DR_MAX_ITERS + 1]  # upstream's entries alias the running loss (:624,630)
+                losses["loss/%d_%d" % (scale, it)] = v[VDR.FINAL_RUNNING]  # upstream's entries alias the running loss (:624,630)
                 if it > 0:
-                    losses["consistency_loss/%d_%d" % (scale, it)] = v[4 * it + 1]
+                    losses["consistency_loss/%d_%d" % (scale, it)] = v[4 * it + VDR.CONSISTENCY]
         losses["loss"] = total / self.num_scales if self.num_scales != 1 else total
         if pu_total is not None:  # process_batch merges the two dictionaries: "loss" is in both and is summed (:337-343)
             losses["reproj_loss/pose_0"] = losses["loss/pose_0_0"] = pu_total

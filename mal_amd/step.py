@@ -9,18 +9,67 @@ op; ``tests/test_gpu_step.py`` holds the two against each other and against the 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import inspect
+from collections import namedtuple
+from typing import Any, NamedTuple
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
-from . import ops
+from . import config, loss_utils, ops
 
-_WS = {}
 _NOISE_COUNTER = {}  # per device: the step number of the "philox" noise stream, a device word the step itself advances
-MAP_NAMES = ("mono_reproj", "multi_reproj", "consistency_mask", "ens_reproj", "noise", "dec_teacher", "dec_student")
+
+
+# The records the autograd functions take as ``consts`` / ``cfg``.  They ARE tuples in the positional order the functions
+# have always read (a plain tuple of any length accepted before still is: forward() normalises with ``StepCfg(*cfg)``).
+class StepConsts(NamedTuple):
+    color0: Any; color_m1: Any; color_p1: Any; K: Any; inv_K: Any
+    cmask: Any; keep: Any  # outputs["consistency_mask"]; (B,) 1 - augmentation_mask, or the mask itself (cfg.aug_is_mask)
+    lowest: Any; noise: Any  # outputs["lowest_cost"]; (B,1,H,W) N(0,1), None with cfg.philox
+
+
+class StepCfg(NamedTuple):
+    min_depth: float; max_depth: float; no_ens: bool; w_main: float; w_distil: float; want_maps: bool; aug_is_mask: bool
+    want_decisions: bool  # parity instrumentation (tests): the kernels' per-pixel decisions, MAL_DEC_* planes
+    philox: Any           # None, or (seed, want the drawn values back)
+    dual_distil: bool = False
+
+
+class MsConsts(NamedTuple):
+    colors: Any; colors_s: Any  # (color0, color_m1, color_p1); inputs[("color", 0, s)] for s = 1..sclm
+    K: Any; inv_K: Any; cmask: Any; keep: Any
+    lowest: Any; noises: Any  # nullable: no matching mask; one (B,1,H,W) map per scale, or None
+
+
+class MsCfg(NamedTuple):
+    min_depth: float; max_depth: float; sclm: int; aug_is_mask: bool
+    philox: Any; want_maps: bool  # None, or the seed
+    hint: Any = None; no_ssim: bool = False  # --temporal: (image_synthesis, inputs, mono_outputs)
+    extra_flags: int = 0          # MAL_STEP_NO_MOTION_MASK | MAL_STEP_NO_AUG | MAL_STEP_ENSEMBLE
+    want_decisions: bool = False  # parity instrumentation (tests): per-scale decision planes
+
+
+Kept = namedtuple("Kept", "tens cons ws losses total")  # ctx.keep: the C struct holds raw pointers, these keep the tensors alive
+
+
+class V16:
+    """slots of the 16-float loss vector of mal_loss_step_fwd (include/mal_hip.h:244-246)"""
+    REPROJ_T, SMOOTH_T, LOSS_T, REPROJ_S, CONSISTENCY, SMOOTH_S, DISTIL, LOSS_MAIN, TOTAL, REPROJ_BOTH, LOSS_PLAIN, LOSS_BLC = range(12)
+
+
+class V48:
+    """slots of the 48-float loss vector of mal_loss_multiscale_fwd (include/mal_hip.h:448-451): ``at(net, scale, term)`` with
+    net 0 the teacher, then the totals and the per-scale sums"""
+    REPROJ, CONSISTENCY, SMOOTH, LOSS = range(4)
+    TEACHER, STUDENT = 0, 1
+    TEACHER_TOTAL, STUDENT_TOTAL, TOTAL = 32, 33, 34
+    REPROJ_BOTH, LOSS_BOTH, ENSEMBLE = 36, 40, 44  # + scale
+    at = staticmethod(lambda net, s, term: (net * L.MS_MAX_SCALES + s) * 4 + term)
 
 
 def noise_counter(dev):
@@ -34,42 +83,54 @@ def noise_counter(dev):
 _WS_SLOT = 0
 
 
-class workspace_slot:
+@contextlib.contextmanager
+def workspace_slot(slot):
     """``with workspace_slot(k): loss_step(...)``: the steps issued inside keep their intermediate maps in workspace number
     ``k`` of this (device, stream, shape) instead of the shared one -- k steps in flight on ONE stream then do not overwrite
     each other's maps (a trainer that runs the backward of a step before the next forward never needs it; bench.py rotates
     over several batches with it, so that no step finds the previous replay's working set in the Infinity Cache)."""
+    global _WS_SLOT
+    prev, _WS_SLOT = _WS_SLOT, int(slot)
+    try:
+        yield
+    finally:
+        _WS_SLOT = prev
 
-    def __init__(self, slot):
-        self.slot = int(slot)
 
-    def __enter__(self):
-        global _WS_SLOT
-        self.prev, _WS_SLOT = _WS_SLOT, self.slot
-        return self
+_BUFFERS = {}  # every cached device buffer of the one-call steps, by (kind, device index, stream, workspace slot, *rest)
 
-    def __exit__(self, *exc):
-        global _WS_SLOT
-        _WS_SLOT = self.prev
-        return False
+
+def _cached(kind, dev, rest, make, fits=lambda buf: True):
+    """the buffer of this kind on this device, stream and workspace slot: made on first use, again only when it no longer
+    ``fits`` (rotating batches keep their own, a graph replay finds the captured ones)"""
+    key = (kind, dev.index, ops._stream(), _WS_SLOT, *rest)
+    buf = _BUFFERS.get(key)
+    if buf is None or not fits(buf):
+        buf = _BUFFERS[key] = make()
+    return buf
+
+
+def byte_workspace(kind, dev, need, *rest):
+    """grow-only device byte workspace of a step family (``kind``) and shape (``rest``)"""
+    return _cached(kind, dev, rest, lambda: torch.empty(need, dtype=torch.uint8, device=dev), lambda ws: ws.numel() >= need)
 
 
 def _workspace(dev, B, H, W):
-    need = L.load().mal_step_workspace_bytes(B, H, W)
-    key = (dev.index, ops._stream(), B, H, W, _WS_SLOT)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _WS[key] = ws
-    return ws
+    return byte_workspace("step", dev, L.load().mal_step_workspace_bytes(B, H, W), B, H, W)
+
+
+def map_names(cfg):
+    """the per-pixel maps a single-scale step with this StepCfg returns, in output order"""
+    names = ["mono_reproj", "multi_reproj", "consistency_mask"] + ([] if cfg.no_ens else ["ens_reproj"]) if cfg.want_maps else []
+    names += ["noise"] if cfg.philox is not None and cfg.philox[1] else []
+    return names + (["dec_teacher", "dec_student"] if cfg.want_decisions else [])
 
 
 def _build_args(disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, temporal=False, ens_disp=None, main_temporal=False):
     """the mal_step_args block of one step, the tensors it points to (kept alive by the caller) and the map dict;
     ``ens_disp`` (--learn_ens): a seventh leaf, appended to the kept tensors"""
     color0, color_m1, color_p1, K, inv_K, cmask, keep, lowest, noise = consts
-    min_depth, max_depth, no_ens, w_main, w_distil, want_maps, aug_is_mask, want_dec, philox = cfg[:9]
-    dual = len(cfg) > 9 and cfg[9]
+    no_ens, aug_is_mask, philox = cfg.no_ens, cfg.aug_is_mask, cfg.philox
     req = ops._req
     tens = [req(t, n) for t, n in ((disp_t, "disp_teacher"), (disp_s, "disp_student"), (aa_m1, "axisangle"),
                                    (tr_m1, "translation"), (aa_p1, "axisangle"), (tr_p1, "translation"))]
@@ -89,16 +150,16 @@ def _build_args(disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, tempora
     dev = tens[0].device
     a = L.StepArgs()
     a.B, a.H, a.W = B, H, W
-    a.min_depth, a.max_depth = float(min_depth), float(max_depth)
+    a.min_depth, a.max_depth = float(cfg.min_depth), float(cfg.max_depth)
     a.flags = (L.STEP_NO_ENS if no_ens else 0) | (L.STEP_AUG_MASK if aug_is_mask else 0) | (L.STEP_TEMPORAL if temporal else 0) | \
-              (L.STEP_DUAL_DISTIL if (dual and no_ens) else 0) | (L.STEP_MAIN_TEMPORAL if main_temporal else 0) | \
+              (L.STEP_DUAL_DISTIL if (cfg.dual_distil and no_ens) else 0) | (L.STEP_MAIN_TEMPORAL if main_temporal else 0) | \
               (L.STEP_TEXEL_INPUTS if texel_inputs else 0)  # (upstream reads dual_distil on the two-way branch only)
     if philox is not None:  # (seed, want the drawn values back)
         a.flags |= L.STEP_NOISE_PHILOX
         a.noise_seed = int(philox[0]) & 0xFFFFFFFFFFFFFFFF
         ctr = noise_counter(tens[0].device)
         a.noise_counter = ctr.data_ptr()
-    a.w_main, a.w_distil = float(w_main), float(w_distil)
+    a.w_main, a.w_distil = float(cfg.w_main), float(cfg.w_distil)
     p = ops._p
     a.disp_teacher, a.disp_student = p(tens[0]), p(tens[1])
     a.axisangle_m1, a.translation_m1, a.axisangle_p1, a.translation_p1 = (p(t) for t in tens[2:6])
@@ -110,30 +171,29 @@ def _build_args(disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, tempora
     total = torch.empty(1, dtype=torch.float32, device=dev)  # its own tensor: no select/copy nodes in the backward
     a.losses, a.loss_total = p(losses), p(total)
     maps = {}
-    if want_maps:
-        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        maps = dict(mono_reproj=new((B, 1, H, W)), multi_reproj=new((B, 1, H, W)),
-                    consistency_mask=new((B, H, W)))
-        if not no_ens:
-            maps["ens_reproj"] = new((B, 1, H, W))
-        a.mono_reproj, a.multi_reproj = p(maps["mono_reproj"]), p(maps["multi_reproj"])
-        a.consistency_mask_out = p(maps["consistency_mask"])
-        a.ens_reproj = p(maps.get("ens_reproj"))
-    if philox is not None and philox[1]:
-        maps["noise"] = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        a.noise_out = p(maps["noise"])
-    if want_dec:  # parity instrumentation (tests): the kernels' per-pixel decisions, MAL_DEC_* planes
-        for k in ("dec_teacher", "dec_student"):
+    for k in map_names(cfg):
+        if k.startswith("dec_"):  # the kernels' per-pixel decisions, MAL_DEC_* planes
             maps[k] = torch.zeros((L.DEC_PLANES, B, H, W), dtype=torch.int32, device=dev)
-        a.dec_teacher, a.dec_student = p(maps["dec_teacher"]), p(maps["dec_student"])
+        else:
+            maps[k] = torch.empty((B, H, W) if k == "consistency_mask" else (B, 1, H, W), dtype=torch.float32, device=dev)
+    (a.mono_reproj, a.multi_reproj, a.consistency_mask_out, a.ens_reproj, a.noise_out, a.dec_teacher, a.dec_student) = (
+        p(maps.get(k)) for k in ("mono_reproj", "multi_reproj", "consistency_mask", "ens_reproj", "noise", "dec_teacher", "dec_student"))
     ws = _workspace(dev, B, H, W)
     a.ws, a.ws_bytes, a.stream = p(ws), ws.numel(), ops._stream()
-    return a, (tens, cons, ws, losses, total), maps
+    return a, Kept(tens, cons, ws, losses, total), maps
 
 
-def _run_bwd(ctx, g_total):
-    tens = ctx.keep[0]
-    ops.check_workspace(ctx.keep[2], ctx.ws_token, "loss_step backward")
+def _input_positions(fn):
+    """(inputs of the autograd function, position of ``ens_disp``): needs_input_grad and backward's result follow the signature"""
+    names = list(inspect.signature(fn.forward).parameters)[1:]  # (without ctx)
+    return len(names), names.index("ens_disp")
+
+
+def _run_bwd(ctx, g_total, fn):
+    """backward of ``fn`` (LossStepFn / TemporalLossStepFn): gradients for the six leaves and, at its position, ens_disp"""
+    n_inputs, ens_index = fn.INPUTS
+    tens = ctx.keep.tens
+    ops.check_workspace(ctx.keep.ws, ctx.ws_token, "loss_step backward")
     # only the total is differentiable through this node: the 16 slots are its terms, for logging
     g_total = g_total.reshape(1).contiguous()
     a = ctx.args
@@ -142,12 +202,23 @@ def _run_bwd(ctx, g_total):
     (a.g_disp_teacher, a.g_disp_student, a.g_axisangle_m1, a.g_translation_m1, a.g_axisangle_p1,
      a.g_translation_p1) = (ops._p(g) for g in grads)
     g_ens = None
-    if len(tens) > 6 and ctx.needs_input_grad[ctx.ens_index]:  # --learn_ens: the ensemble head's disparity
+    if len(tens) > 6 and ctx.needs_input_grad[ens_index]:  # --learn_ens: the ensemble head's disparity
         g_ens = torch.empty_like(tens[6])
         a.g_ens_disp = ops._p(g_ens)
     L.check(L.load().mal_loss_step_bwd(C.byref(a)), "mal_loss_step_bwd")
-    ctx.g_ens = g_ens
-    return grads
+    out = grads + [None] * (n_inputs - len(grads))
+    out[ens_index] = g_ens
+    return tuple(out)
+
+
+def _end_fwd(ctx, a, keep, maps):
+    """what both single-scale forwards leave for the backward, and their outputs: total, the 16 slots, the maps"""
+    ctx.args, ctx.keep = a, keep  # the C struct holds raw pointers: keep the tensors alive
+    ctx.ws_token = ops.claim_workspace(keep.ws)
+    ctx.set_materialize_grads(False)
+    outs = (keep.total, keep.losses, *maps.values())  # (the maps in map_names(cfg) order)
+    ctx.mark_non_differentiable(*outs[1:])
+    return outs
 
 
 class LossStepFn(Function):
@@ -155,51 +226,43 @@ class LossStepFn(Function):
 
     @staticmethod
     def forward(ctx, disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, ens_disp=None):
+        consts, cfg = StepConsts(*consts), StepCfg(*cfg)
         a, keep, maps = _build_args(disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, ens_disp=ens_disp)
         L.check(L.load().mal_loss_step_fwd(C.byref(a)), "mal_loss_step_fwd")
         if _CAPTURE is not None:
             _CAPTURE.append((a, keep))
-        ctx.args = a
-        ctx.ens_index = 8
-        ctx.keep = keep  # the C struct holds raw pointers: keep the tensors alive
-        ctx.ws_token = ops.claim_workspace(keep[2])
-        ctx.set_materialize_grads(False)
-        outs = [keep[4], keep[3]] + [maps[k] for k in MAP_NAMES if k in maps]
-        ctx.mark_non_differentiable(*outs[1:])
-        return tuple(outs)
+        return _end_fwd(ctx, a, keep, maps)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_total, *_):
         if g_total is None:
-            return (None,) * 9
-        grads = _run_bwd(ctx, g_total)
-        return (*grads, None, None, ctx.g_ens)
+            return (None,) * LossStepFn.INPUTS[0]
+        return _run_bwd(ctx, g_total, LossStepFn)
 
 
-class _Hint:
-    """One pass's exchange with the temporal hint's producer: the teacher's (``--temporal``, mal_step_args.warp_* / syn_* /
-    g_syn_* / g_warp_* / syn_region) or the student's (``--main_temporal``, the ``*_s_*`` members)."""
+LossStepFn.INPUTS = _input_positions(LossStepFn)
 
-    def __init__(self, a, student, B, H, W, dev, scale=None):
-        """``scale`` (mal_ms_args, one hint per scale): the members are arrays indexed by it and the sparse bit lives in
-        ``syn_sparse``; None: mal_step_args"""
+
+class _HintIO:
+    """What ``_Hint`` and ``_ScaleHint`` share: the buffers of one (pass, scale) the producer is called on, their pointers in
+    the argument block, the producer call and what is exposed of its answer."""
+
+    def __init__(self, a, student, scale, pair, pre):
+        """``a``: the argument block; ``scale``: index into its per-scale arrays, None where its members are plain pointers"""
         self.a, self.tag, self.student, self.scale = a, "_s" if student else "", student, scale
-        self.sparse_flag = L.STEP_SYN_S_SPARSE if student else L.STEP_SYN_SPARSE
-        self.sparse = False
-        self.shape, self.dev = (B, 3, H, W), dev
         # the two warped images of a sample side by side: the (2,3,H,W) pair the instance segmenter is fed is then a VIEW
-        # (upstream stacks it per sample, dyn_utils.py:139-140); ("color", f, 0) are the two batch-strided halves
-        self.pair = torch.empty((B, 2, 3, H, W), dtype=torch.float32, device=dev)
-        self.warp = [self.pair[:, 0], self.pair[:, 1]]
+        # (upstream stacks it per sample, dyn_utils.py:139-140); ("color", f, scale) are the two batch-strided halves
+        self.pair = pair
+        self.warp = [pair[:, 0], pair[:, 1]]
         self._set("warp", self.warp)
         # The buffers the synthesised images are made in are NOT filled: a producer that knows the key
         # ("syn_sparse_buffers", scale) -- mal_amd.dyn_utils.image_synthesis -- writes only the pixels of its instances'
         # regions into them instead of cloning every sample first (dyn_utils.py:127-128) and says so (("syn_sparse", scale),
         # with the region map); the sweep then reads the warped images everywhere else (MAL_STEP_SYN_SPARSE), so the pass in
         # front of the producer writes them once, not twice
-        self.pre = [torch.empty(self.shape, dtype=torch.float32, device=dev) for _ in range(2)]
-        self.has_ins, self.region, self.snap, self.syn, self.syn_data, self.leaf, self.g_syn = False, None, None, None, None, None, None
+        self.pre = pre
+        self.has_ins, self.local = False, None
 
     def _put(self, name, ptr):
         if self.scale is None:
@@ -211,6 +274,42 @@ class _Hint:
         for t, sfx in zip(tensors, tail):
             self._put(base + self.tag + sfx, t.data_ptr())
 
+    def _call(self, synth, inputs, colors):
+        """the producer on this scale's warped images (``colors``: the tensors it finds them under)"""
+        sc = self.scale or 0
+        local = {("color", -1, sc): colors[0], ("color", 1, sc): colors[1], ("color_pair", sc): self.pair,
+                 ("syn_sparse_buffers", sc): (self.pre[0], self.pre[1])}
+        self.has_ins = bool(synth(inputs, local, sc))
+        self.local = local
+
+    def _expose(self, out, dense, syn, region):
+        """what the reference's generate_images_pred leaves in the pass's outputs dict (trainer.py:1122-1125,1161-1165):
+        ("color", f, scale) and, with ``syn`` (None: the producer wrote none), ("syn", f, scale); ``region``: a sparse
+        producer's map, None for a dense one"""
+        sc = self.scale or 0
+        out[("color", -1, sc)], out[("color", 1, sc)] = self.warp
+        if syn is not None and region is None:
+            out[("syn", -1, sc)], out[("syn", 1, sc)] = syn
+        elif syn is not None and dense:
+            # dense images for the caller (logging) only when maps are wanted: outside the regions syn IS the warped image
+            inside = (region & 1).bool().unsqueeze(1)
+            out[("syn", -1, sc)], out[("syn", 1, sc)] = (torch.where(inside, t, w_) for t, w_ in zip(syn, self.warp))
+
+
+class _Hint(_HintIO):
+    """One pass's exchange with the temporal hint's producer: the teacher's (``--temporal``, mal_step_args.warp_* / syn_* /
+    g_syn_* / g_warp_* / syn_region) or the student's (``--main_temporal``, the ``*_s_*`` members)."""
+
+    def __init__(self, a, student, B, H, W, dev, scale=None):
+        """``scale`` (mal_ms_args, one hint per scale): the members are arrays indexed by it and the sparse bit lives in
+        ``syn_sparse``; None: mal_step_args"""
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        super().__init__(a, student, scale, new((B, 2, 3, H, W)), [new((B, 3, H, W)) for _ in range(2)])
+        self.sparse_flag = L.STEP_SYN_S_SPARSE if student else L.STEP_SYN_SPARSE
+        self.sparse = False
+        self.shape, self.dev = (B, 3, H, W), dev
+        self.region, self.snap, self.syn, self.syn_data, self.leaf, self.g_syn = None, None, None, None, None, None
+
     def _mark_sparse(self):
         self.sparse = True
         if self.scale is None:
@@ -221,14 +320,9 @@ class _Hint:
     def produce(self, synth, inputs, defer=False):
         """between mal_loss_step_warp and mal_loss_step_fwd; anything raised here is the caller's to abort the step on.
         ``defer``: the caller calls ``finish`` itself (with the has_ins every scale is to use)"""
-        B, _, H, W = self.shape
-        sc = self.scale or 0
         with torch.enable_grad():
             self.leaf = [w.detach().requires_grad_(True) for w in self.warp]
-            local = {("color", -1, sc): self.leaf[0], ("color", 1, sc): self.leaf[1], ("color_pair", sc): self.pair,
-                     ("syn_sparse_buffers", sc): (self.pre[0], self.pre[1])}
-            self.has_ins = bool(synth(inputs, local, sc))
-        self.local = local
+            self._call(synth, inputs, self.leaf)
         if not defer:
             self.finish()
 
@@ -274,17 +368,7 @@ class _Hint:
         self._set("g_syn", self.g_syn)
 
     def expose(self, out, dense):
-        """what the reference's generate_images_pred leaves in the pass's outputs dict (trainer.py:1122-1125,1161-1165)"""
-        sc = self.scale or 0
-        out[("color", -1, sc)], out[("color", 1, sc)] = self.warp
-        if self.has_ins:
-            if self.sparse:
-                # dense images for the caller (logging) only when maps are wanted: outside the regions syn IS the warped image
-                if dense:
-                    inside = (self.region & 1).bool().unsqueeze(1)
-                    out[("syn", -1, sc)], out[("syn", 1, sc)] = (torch.where(inside, t, w_) for t, w_ in zip(self.syn_data, self.warp))
-            else:
-                out[("syn", -1, sc)], out[("syn", 1, sc)] = self.syn_data
+        self._expose(out, dense, self.syn_data if self.has_ins else None, self.region if self.sparse else None)
         out["multi_has_ins" if self.student else "has_ins"] = self.has_ins
 
     def backward(self, stream=None):
@@ -318,57 +402,31 @@ class _Hint:
         return on_stream
 
 
-_SCALE_BUFS = {}
-
-
 def _scale_buffers(dev, B, H, W, student, s):
-    """the (B,2,3,H,W) warped pair and the two syn buffers of scale ``s`` > 0 of a pass, kept per (device, stream, shape,
-    workspace slot): rotating batches (``workspace_slot``) keep their own, a graph replay finds the captured ones"""
-    key = (dev.index, ops._stream(), B, H, W, _WS_SLOT, student, s)
-    bufs = _SCALE_BUFS.get(key)
-    if bufs is None:
-        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        bufs = _SCALE_BUFS[key] = (new((B, 2, 3, H, W)), new((B, 3, H, W)), new((B, 3, H, W)))
-    return bufs
+    """the (B,2,3,H,W) warped pair and the two syn buffers of scale ``s`` > 0 of a pass, cached like the workspaces"""
+    new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    return _cached("scale_hint", dev, (B, H, W, student, s), lambda: (new((B, 2, 3, H, W)), new((B, 3, H, W)), new((B, 3, H, W))))
 
 
-class _ScaleHint:
+class _ScaleHint(_HintIO):
     """Scale ``s`` > 0 of a hinted pass with --distil (mal_step_scales_args): generate_images_pred warps the full-resolution
     sources with ("disp", s) upsampled and calls the producer on them (trainer.py:1088-1165), but no loss reads what it
     leaves -- only its answer counts, and only the last scale's.  Forward only: the warped images carry no gradient and no
     backward is ever run for them."""
 
     def __init__(self, sa, student, s, B, H, W, dev):
-        self.student, self.scale = student, s
-        self.pair, pre0, pre1 = _scale_buffers(dev, B, H, W, student, s)
-        self.pre = (pre0, pre1)
-        self.warp = [self.pair[:, 0], self.pair[:, 1]]
-        tag = "_s" if student else ""
-        getattr(sa, "warp" + tag + "_m1")[s], getattr(sa, "warp" + tag + "_p1")[s] = (t.data_ptr() for t in self.warp)
-        self.has_ins, self.local = False, None
+        pair, pre0, pre1 = _scale_buffers(dev, B, H, W, student, s)
+        super().__init__(sa, student, s, pair, (pre0, pre1))
 
     def produce(self, synth, inputs):
-        sc = self.scale
-        local = {("color", -1, sc): self.warp[0], ("color", 1, sc): self.warp[1], ("color_pair", sc): self.pair,
-                 ("syn_sparse_buffers", sc): self.pre}
         with torch.no_grad():
-            self.has_ins = bool(synth(inputs, local, sc))
-        self.local = local
+            self._call(synth, inputs, self.warp)
 
     def expose(self, out, dense):
         """("color", f, s) and, where the producer wrote them, ("syn", f, s), as _Hint.expose does for scale 0"""
         sc, local = self.scale, self.local
-        out[("color", -1, sc)], out[("color", 1, sc)] = self.warp
-        if ("syn", -1, sc) not in local:
-            return
-        syn = [local[("syn", -1, sc)], local[("syn", 1, sc)]]
-        region = local.get(("syn_region", sc))
-        if local.get(("syn_sparse", sc)) and region is not None:
-            if dense:  # outside its regions a sparse producer's syn IS the warped image
-                inside = (region & 1).bool().unsqueeze(1)
-                out[("syn", -1, sc)], out[("syn", 1, sc)] = (torch.where(inside, t, w_) for t, w_ in zip(syn, self.warp))
-        else:
-            out[("syn", -1, sc)], out[("syn", 1, sc)] = (t.detach() for t in syn)
+        syn = [local[("syn", f, sc)].detach() for f in (-1, 1)] if ("syn", -1, sc) in local else None
+        self._expose(out, dense, syn, local.get(("syn_region", sc)) if local.get(("syn_sparse", sc)) else None)
 
 
 class TemporalLossStepFn(Function):
@@ -386,11 +444,11 @@ class TemporalLossStepFn(Function):
                 scales=None):
         """``scales`` (--distil with sclm > 0): (sclm, teacher's ("disp", s) for s = 1..sclm, the student's) -- scale s of
         every hinted pass is warped by mal_loss_step_warp_scales and handed to the producer after scale 0 (_ScaleHint)"""
+        consts, cfg = StepConsts(*consts), StepCfg(*cfg)
         a, keep, maps = _build_args(disp_t, disp_s, aa_m1, tr_m1, aa_p1, tr_p1, consts, cfg, temporal=which[0],
                                     main_temporal=which[1], ens_disp=ens_disp)
-        ctx.ens_index = 12
-        B, _, H, W = keep[0][0].shape
-        dev = keep[0][0].device
+        B, _, H, W = keep.tens[0].shape
+        dev = keep.tens[0].device
         hints = [_Hint(a, student, B, H, W, dev) for student, on in ((False, which[0]), (True, which[1])) if on]
         a.warp_sample_stride = 6 * H * W
         extra, sa, low = {h.student: [] for h in hints}, None, ()
@@ -421,23 +479,17 @@ class TemporalLossStepFn(Function):
             lib.mal_loss_step_abort(C.byref(a))
             raise
         L.check(lib.mal_loss_step_fwd(C.byref(a)), "mal_loss_step_fwd")
-        ctx.args, ctx.keep = a, keep
-        ctx.ws_token = ops.claim_workspace(keep[2])
         ctx.hints, ctx.scale_hints = hints, (low, extra)  # the C structs hold their buffers' pointers
-        ctx.set_materialize_grads(False)
         for h in hints:
-            h.expose(expose[1] if h.student else expose[0], cfg[5])
-            for e in extra[h.student]:
-                e.expose(expose[1] if h.student else expose[0], cfg[5])
-        outs = [keep[4], keep[3]] + [maps[k] for k in MAP_NAMES if k in maps]
-        ctx.mark_non_differentiable(*outs[1:])
-        return tuple(outs)
+            for e in (h, *extra[h.student]):
+                e.expose(expose[1] if h.student else expose[0], cfg.want_maps)
+        return _end_fwd(ctx, a, keep, maps)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_total, *_):
         if g_total is None:
-            return (None,) * 14
+            return (None,) * TemporalLossStepFn.INPUTS[0]
         # option "tail_overlap": the backward chain (producer's backward -> teacher's gradient sweep) on the library's side
         # stream, behind the fused sweep only -- beside the epilogue and the reduction the forward left on this stream
         lib, a = L.load(), ctx.args
@@ -451,8 +503,44 @@ class TemporalLossStepFn(Function):
         finally:
             if side.value != a.stream and not (overlap and ok):  # nothing (or not everything) went there: join it back now
                 L.check(lib.mal_loss_step_tail_cancel(C.byref(a)), "mal_loss_step_tail_cancel")
-        grads = _run_bwd(ctx, g_total)
-        return (*grads, None, None, None, None, None, None, ctx.g_ens, None)
+        return _run_bwd(ctx, g_total, TemporalLossStepFn)
+
+
+TemporalLossStepFn.INPUTS = _input_positions(TemporalLossStepFn)
+
+
+# ---------------------------------------------------------------------------------- input preparation of the one-call steps
+def aug_keep(opt, outputs, B):
+    """outputs["augmentation_mask"] (its first ``opt.batch_size`` rows) -> (keep, aug_is_mask): a contiguous float32 mask is
+    passed as itself and 1 - mask is formed on the device; anything else as 1 - mask in float32"""
+    aug = outputs["augmentation_mask"][:opt.batch_size]
+    if aug.dtype == torch.float32 and aug.is_contiguous():
+        return aug.reshape(B), True
+    if not aug.is_floating_point():
+        aug = aug.to(torch.float32)  # (a bool mask: torch refuses 1 - mask)
+    return (1 - aug).to(torch.float32).reshape(B), False
+
+
+def pose_leaves(mono_outputs):
+    """axisangle_m1, translation_m1, axisangle_p1, translation_p1 out of ``mono_outputs``"""
+    aa = [mono_outputs[("axisangle", 0, f)] for f in (-1, 1)]
+    tr = [mono_outputs[("translation", 0, f)] for f in (-1, 1)]
+    fix = lambda t: t[:, 0] if t.dim() == 4 else t  # the pose decoder emits (B,2,1,3); frame 0 of it is used
+    return fix(aa[0]), fix(tr[0]), fix(aa[1]), fix(tr[1])
+
+
+def draw_noise_maps(shape, dev, n, dead):
+    """The tie-break noise of a step as ``config.noise_source`` says -> (n maps of ``shape``, None) or (None, philox seed).
+    "philox": drawn inside the step's first kernel -- no RNG launch, no host work, no generator touched.  "cpu": the n maps,
+    then ``dead`` more draws whose values nobody reads: the reference makes them (loss_utils.py:178 in compute_main_losses,
+    trainer.py:1305-1308,1325 for the student's scales), so the global CPU generator stays on its stream.  "cuda": the n maps."""
+    if config.noise_source == "philox":
+        return None, config.noise_seed
+    maps = [loss_utils.draw_noise(shape, dev) for _ in range(n)]
+    if config.noise_source == "cpu":
+        for _ in range(dead):
+            torch.randn(shape)
+    return maps, None
 
 
 def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=None, noise=None, want_maps=True,
@@ -475,7 +563,6 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
     ``want_decisions`` (tests) adds ``maps["dec_teacher"]`` / ``["dec_student"]``: the per-pixel decisions of the two
     gradient passes (int32 (MAL_DEC_PLANES,B,H,W), include/mal_hip.h).
     Returns (losses dict, loss_list or None, maps dict)."""
-    from . import config, loss_utils
     sclm = int(getattr(opt, "sclm", 0))
     if getattr(opt, "no_ssim", False) or not getattr(opt, "distil", True):
         # (--no_ssim is read by Trainer.compute_reprojection_loss, trainer.py:1217, i.e. on the non-distil route only: the
@@ -519,52 +606,37 @@ def loss_step(opt, inputs, mono_outputs, outputs, w_list=None, batch_size_scale=
                     raise L.MalError("loss_step: %s[('disp', %d)] must be a float32 (B,1,H>>%d,W>>%d) = %s tensor on %s; got %s %s"
                                      % (name, s, s, s, (B, 1, H >> s, W >> s), dev, tuple(t.shape), t.dtype))
         scales = (sclm, low["mono_outputs"], low["outputs"])
-    aa = {f: mono_outputs[("axisangle", 0, f)] for f in (-1, 1)}
-    tr = {f: mono_outputs[("translation", 0, f)] for f in (-1, 1)}
-    fix = lambda t: t[:, 0] if t.dim() == 4 else t  # the pose decoder emits (B,2,1,3); frame 0 of it is used
+    poses = pose_leaves(mono_outputs)
     if noise is not None and tuple(noise.shape) != (B, 1, H, W):
         raise L.MalError("loss_step: the tie-break noise must be (B,1,H,W) = %s; got %s" % ((B, 1, H, W), tuple(noise.shape)))
     philox = None
     if noise is None:  # (loss_utils.compute_mono_losses adds the noise whatever --disable_automasking says, loss_utils.py:105-106)
-        if config.noise_source == "philox":  # drawn inside the step's first kernel: no RNG launch, no host work
-            philox = (config.noise_seed, bool(want_noise))
-        else:
-            noise = loss_utils.draw_noise((B, 1, H, W), dev)
-            if config.noise_source == "cpu":
-                torch.randn((B, 1, H, W))  # compute_main_losses' dead draw (loss_utils.py:178)
-    aug = outputs["augmentation_mask"][:opt.batch_size]
-    aug_is_mask = aug.dtype == torch.float32 and aug.is_contiguous()  # then 1 - mask is formed on the device
-    if not aug_is_mask and not aug.is_floating_point():
-        aug = aug.to(torch.float32)  # (a bool mask: torch refuses 1 - mask)
-    keep = aug.reshape(B) if aug_is_mask else (1 - aug).to(torch.float32).reshape(B)
+        drawn, seed = draw_noise_maps((B, 1, H, W), dev, 1, 1)
+        noise, philox = (None, (seed, bool(want_noise))) if drawn is None else (drawn[0], None)
+    keep, aug_is_mask = aug_keep(opt, outputs, B)
     blc = bool(getattr(opt, "loss_blc", False))
     w_main, w_distil = 1.0, 1.0
     if blc:
         scale = float(batch_size_scale if batch_size_scale is not None else opt.batch_size)
         w_main, w_distil = scale * float(w_list[0]), scale * float(w_list[1])
-    consts = (color0, inputs[("color", -1, 0)], inputs[("color", 1, 0)], inputs[("K", 0)], inputs[("inv_K", 0)],
-              outputs["consistency_mask"].to(torch.float32), keep, outputs["lowest_cost"], noise)
-    cfg = (opt.min_depth, opt.max_depth, bool(getattr(opt, "no_ens", False)), w_main, w_distil, bool(want_maps),
-           aug_is_mask, bool(want_decisions), philox, bool(getattr(opt, "dual_distil", False)))
+    consts = StepConsts(color0, inputs[("color", -1, 0)], inputs[("color", 1, 0)], inputs[("K", 0)], inputs[("inv_K", 0)],
+                        outputs["consistency_mask"].to(torch.float32), keep, outputs["lowest_cost"], noise)
+    cfg = StepCfg(opt.min_depth, opt.max_depth, bool(getattr(opt, "no_ens", False)), w_main, w_distil, bool(want_maps),
+                  aug_is_mask, bool(want_decisions), philox, bool(getattr(opt, "dual_distil", False)))
     if temporal or main_temporal:
-        res = TemporalLossStepFn.apply(mono_outputs[("disp", 0)], outputs[("disp", 0)], fix(aa[-1]), fix(tr[-1]), fix(aa[1]),
-                                       fix(tr[1]), consts, cfg, image_synthesis, inputs, (mono_outputs, outputs),
-                                       (temporal, main_temporal), ens_disp, scales)
+        res = TemporalLossStepFn.apply(mono_outputs[("disp", 0)], outputs[("disp", 0)], *poses, consts, cfg, image_synthesis,
+                                       inputs, (mono_outputs, outputs), (temporal, main_temporal), ens_disp, scales)
     else:
-        res = LossStepFn.apply(mono_outputs[("disp", 0)], outputs[("disp", 0)], fix(aa[-1]), fix(tr[-1]), fix(aa[1]),
-                               fix(tr[1]), consts, cfg, ens_disp)
+        res = LossStepFn.apply(mono_outputs[("disp", 0)], outputs[("disp", 0)], *poses, consts, cfg, ens_disp)
     total, v = res[0].reshape(()), res[1]
-    maps = {}
-    names = (["mono_reproj", "multi_reproj", "consistency_mask"] + ([] if cfg[2] else ["ens_reproj"])) if want_maps else []
-    names += ["noise"] if philox is not None and philox[1] else []
-    names += ["dec_teacher", "dec_student"] if want_decisions else []
-    maps = dict(zip(names, res[2:]))
+    maps = dict(zip(map_names(cfg), res[2:]))
     if want_maps:
         outputs["consistency_mask"] = maps["consistency_mask"]
-    losses = {"reproj_loss/0": v[9], "consistency_loss/0": v[4], "distil_loss": v[6], "loss/0": v[11] if blc else v[10],
-              "loss": total, "mono/reproj_loss/0": v[0], "mono/loss": v[2], "smooth_loss/mono": v[1],
-              "smooth_loss/multi": v[5], "main/reproj_loss/0": v[3]}
-    loss_list = [v[11], v[6]] if blc else None
+    losses = {"reproj_loss/0": v[V16.REPROJ_BOTH], "consistency_loss/0": v[V16.CONSISTENCY], "distil_loss": v[V16.DISTIL],
+              "loss/0": v[V16.LOSS_BLC] if blc else v[V16.LOSS_PLAIN], "loss": total, "mono/reproj_loss/0": v[V16.REPROJ_T],
+              "mono/loss": v[V16.LOSS_T], "smooth_loss/mono": v[V16.SMOOTH_T], "smooth_loss/multi": v[V16.SMOOTH_S],
+              "main/reproj_loss/0": v[V16.REPROJ_S]}
+    loss_list = [v[V16.LOSS_BLC], v[V16.DISTIL]] if blc else None
     return losses, loss_list, maps
 
 
@@ -600,27 +672,14 @@ def teacher_pass_replay(opt, inputs, mono_outputs, outputs, **kw):
 
 
 # ---------------------------------------------------------------------------------- sclm > 0, no --distil
-_WS_MS = {}
-
-
-def _workspace_ms(dev, B, H, W, sclm):
-    need = L.load().mal_ms_workspace_bytes(B, H, W, sclm)
-    key = (dev.index, ops._stream(), B, H, W, sclm, _WS_SLOT)
-    ws = _WS_MS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WS_MS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return ws
-
-
 class MultiScaleLossFn(Function):
     """leaves: disp_teacher[0..sclm], disp_student[0..sclm], axisangle_m1, translation_m1, axisangle_p1, translation_p1"""
 
     @staticmethod
     def forward(ctx, consts, cfg, *leaves):
+        consts, cfg = MsConsts(*consts), MsCfg(*cfg)
         colors, colors_s, K, inv_K, cmask, keep, lowest, noises = consts
-        min_depth, max_depth, sclm, aug_is_mask, philox, want_maps = cfg[:6]
-        hint = cfg[6] if len(cfg) > 6 else None  # --temporal: (image_synthesis, inputs, mono_outputs)
-        want_dec = len(cfg) > 9 and cfg[9]         # parity instrumentation (tests): per-scale decision planes
+        sclm, philox, hint = cfg.sclm, cfg.philox, cfg.hint
         S = sclm + 1
         if noises is not None and len(noises) != S:
             raise L.MalError("MultiScaleLossFn: one noise map per scale (%d), or None; got %d" % (S, len(noises)))
@@ -636,9 +695,8 @@ class MultiScaleLossFn(Function):
                     raise L.MalError("loss_step_multiscale: the disparity of scale %d must be (B,1,%d,%d)" % (s, H >> s, W >> s))
         a = L.MsArgs()
         a.B, a.H, a.W, a.sclm = B, H, W, sclm
-        a.min_depth, a.max_depth = float(min_depth), float(max_depth)
-        a.flags = (L.STEP_AUG_MASK if aug_is_mask else 0) | (L.STEP_NO_SSIM if (len(cfg) > 7 and cfg[7]) else 0) | \
-                  (int(cfg[8]) if len(cfg) > 8 else 0)
+        a.min_depth, a.max_depth = float(cfg.min_depth), float(cfg.max_depth)
+        a.flags = (L.STEP_AUG_MASK if cfg.aug_is_mask else 0) | (L.STEP_NO_SSIM if cfg.no_ssim else 0) | int(cfg.extra_flags)
         a.color0, a.color_m1, a.color_p1 = (p(t) for t in cons[:3])
         for s in range(1, S):
             a.color0_s[s] = p(cons[3 + s - 1])
@@ -658,18 +716,18 @@ class MultiScaleLossFn(Function):
         total = torch.empty(1, dtype=torch.float32, device=dev)
         a.losses, a.loss_total = p(losses), p(total)
         outs = [total, losses]
-        if want_maps and lowest is not None and not (a.flags & L.STEP_NO_MOTION_MASK):
+        if cfg.want_maps and lowest is not None and not (a.flags & L.STEP_NO_MOTION_MASK):
             cm = torch.empty((B, H, W), dtype=torch.float32, device=dev)
             a.consistency_mask_out = p(cm)
             outs.append(cm)
         decs = []
-        if want_dec:  # one (MAL_DEC_PLANES,B,H,W) int32 block per network and scale (include/mal_hip.h MAL_DEC_*)
+        if cfg.want_decisions:  # one (MAL_DEC_PLANES,B,H,W) int32 block per network and scale (include/mal_hip.h MAL_DEC_*)
             decs = [torch.zeros((L.DEC_PLANES, B, H, W), dtype=torch.int32, device=dev) for _ in range(2 * S)]
             for s in range(S):
                 a.dec_teacher[s], a.dec_student[s] = p(decs[s]), p(decs[S + s])
             outs += decs
         ctx.n_dec = len(decs)
-        ws = _workspace_ms(dev, B, H, W, sclm)
+        ws = byte_workspace("multiscale", dev, L.load().mal_ms_workspace_bytes(B, H, W, sclm), B, H, W, sclm)
         a.ws, a.ws_bytes, a.stream = p(ws), ws.numel(), ops._stream()
         hints = []
         if hint is not None:
@@ -691,9 +749,9 @@ class MultiScaleLossFn(Function):
                 raise
         L.check(L.load().mal_loss_multiscale_fwd(C.byref(a)), "mal_loss_multiscale_fwd")
         for h in hints:
-            h.expose(hint[2], want_maps)
+            h.expose(hint[2], cfg.want_maps)
         ctx.hints = hints  # the argument block holds their buffers' pointers
-        ctx.args, ctx.keep, ctx.S = a, (tens, cons, ws, losses, total), S
+        ctx.args, ctx.keep, ctx.S = a, Kept(tens, cons, ws, losses, total), S
         ctx.ws_token = ops.claim_workspace(ws)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*outs[1:])
@@ -702,11 +760,10 @@ class MultiScaleLossFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_total, *_):
-        tens, S = ctx.keep[0], ctx.S
-        if g_total is not None:
-            ops.check_workspace(ctx.keep[2], ctx.ws_token, "loss_step_multiscale backward")
+        tens, S = ctx.keep.tens, ctx.S
         if g_total is None:
             return (None,) * (2 + len(tens))
+        ops.check_workspace(ctx.keep.ws, ctx.ws_token, "loss_step_multiscale backward")
         g_total = g_total.reshape(1).contiguous()
         a = ctx.args
         grads = [torch.empty_like(t) if ctx.needs_input_grad[2 + i] else None for i, t in enumerate(tens)]
@@ -736,7 +793,6 @@ def loss_step_multiscale(opt, inputs, mono_outputs, outputs, noises=None, want_m
     student's, :614-616; ``losses["loss"]`` carries the gradient), ``mono_losses`` the teacher's own.
     ``want_decisions`` (tests): a third value ``{"dec_teacher": [per scale], "dec_student": [per scale]}`` -- the per-pixel
     decisions of every scale's gradient passes (int32 (MAL_DEC_PLANES,B,H,W) each, include/mal_hip.h)."""
-    from . import config, loss_utils
     sclm = int(getattr(opt, "sclm", 0))
     temporal = bool(getattr(opt, "temporal", False))
     if noises is not None and len(noises) != sclm + 1:
@@ -754,36 +810,23 @@ def loss_step_multiscale(opt, inputs, mono_outputs, outputs, noises=None, want_m
     color0 = inputs[("color", 0, 0)]
     B, _, H, W = color0.shape
     dev = color0.device
-    fix = lambda t: t[:, 0] if t.dim() == 4 else t
-    aa = {f: fix(mono_outputs[("axisangle", 0, f)]) for f in (-1, 1)}
-    tr = {f: fix(mono_outputs[("translation", 0, f)]) for f in (-1, 1)}
+    poses = pose_leaves(mono_outputs)
     philox = None
     if getattr(opt, "disable_automasking", False):
         noises = None  # upstream still compares against the identity term (trainer.py:1296-1311): only the tie-break noise goes
     elif noises is None:
-        if config.noise_source == "philox":
-            philox = config.noise_seed
-        else:
-            noises = [loss_utils.draw_noise((B, 1, H, W), dev) for _ in range(sclm + 1)]
-            if config.noise_source == "cpu":
-                for _ in range(sclm + 1):
-                    torch.randn((B, 1, H, W))  # the student's dead draws (trainer.py:1305-1308,1325)
-    aug = outputs["augmentation_mask"][:opt.batch_size]
-    aug_is_mask = aug.dtype == torch.float32 and aug.is_contiguous()
-    if not aug_is_mask and not aug.is_floating_point():
-        aug = aug.to(torch.float32)  # (a bool mask: torch refuses 1 - mask)
-    keep = aug.reshape(B) if aug_is_mask else (1 - aug).to(torch.float32).reshape(B)
-    consts = ((color0, inputs[("color", -1, 0)], inputs[("color", 1, 0)]), [inputs[("color", 0, s)] for s in range(1, sclm + 1)],
-              inputs[("K", 0)], inputs[("inv_K", 0)], outputs["consistency_mask"].to(torch.float32), keep,
-              outputs.get("lowest_cost"), noises)
-    cfg = (opt.min_depth, opt.max_depth, sclm, aug_is_mask, philox, bool(want_maps),
-           (image_synthesis, inputs, mono_outputs) if temporal else None, bool(getattr(opt, "no_ssim", False)),
-           (L.STEP_NO_MOTION_MASK if getattr(opt, "disable_motion_masking", False) else 0) |
-           (L.STEP_NO_AUG if getattr(opt, "no_matching_augmentation", False) else 0) |
-           (L.STEP_ENSEMBLE if getattr(opt, "ensemble", False) else 0), bool(want_decisions))
-    leaves = [mono_outputs[("disp", s)] for s in range(sclm + 1)] + [outputs[("disp", s)] for s in range(sclm + 1)] + \
-             [aa[-1], tr[-1], aa[1], tr[1]]
-    res = MultiScaleLossFn.apply(consts, cfg, *leaves)
+        noises, philox = draw_noise_maps((B, 1, H, W), dev, sclm + 1, sclm + 1)
+    keep, aug_is_mask = aug_keep(opt, outputs, B)
+    consts = MsConsts((color0, inputs[("color", -1, 0)], inputs[("color", 1, 0)]),
+                      [inputs[("color", 0, s)] for s in range(1, sclm + 1)], inputs[("K", 0)], inputs[("inv_K", 0)],
+                      outputs["consistency_mask"].to(torch.float32), keep, outputs.get("lowest_cost"), noises)
+    cfg = MsCfg(opt.min_depth, opt.max_depth, sclm, aug_is_mask, philox, bool(want_maps),
+                hint=(image_synthesis, inputs, mono_outputs) if temporal else None, no_ssim=bool(getattr(opt, "no_ssim", False)),
+                extra_flags=(L.STEP_NO_MOTION_MASK if getattr(opt, "disable_motion_masking", False) else 0) |
+                (L.STEP_NO_AUG if getattr(opt, "no_matching_augmentation", False) else 0) |
+                (L.STEP_ENSEMBLE if getattr(opt, "ensemble", False) else 0), want_decisions=bool(want_decisions))
+    leaves = [mono_outputs[("disp", s)] for s in range(sclm + 1)] + [outputs[("disp", s)] for s in range(sclm + 1)]
+    res = MultiScaleLossFn.apply(consts, cfg, *leaves, *poses)
     total, v = res[0].reshape(()), res[1]
     n_dec = 2 * (sclm + 1) if want_decisions else 0
     decs = res[len(res) - n_dec:] if n_dec else ()
@@ -797,16 +840,17 @@ def loss_step_multiscale(opt, inputs, mono_outputs, outputs, noises=None, want_m
             _, mono_depth = layers.disp_to_depth(mono_outputs[("disp", 0)].detach(), opt.min_depth, opt.max_depth)
             outputs["consistency_mask"] = ops.matching_mask(outputs["lowest_cost"], mono_depth[:, 0].contiguous(),
                                                             outputs["consistency_mask"].to(torch.float32))
-    losses, mono_losses = {"loss": total}, {"loss": v[32]}
+    losses, mono_losses = {"loss": total}, {"loss": v[V48.TEACHER_TOTAL]}
     for s in range(sclm + 1):
-        losses["reproj_loss/%d" % s], losses["loss/%d" % s] = v[36 + s], v[40 + s]
-        losses["consistency_loss/%d" % s] = v[(4 + s) * 4 + 1]
-        losses["main/reproj_loss/%d" % s], losses["main/loss/%d" % s] = v[(4 + s) * 4], v[(4 + s) * 4 + 3]
-        losses["smooth_loss/multi/%d" % s], mono_losses["smooth_loss/%d" % s] = v[(4 + s) * 4 + 2], v[s * 4 + 2]
+        t, m = (lambda term: v[V48.at(V48.TEACHER, s, term)]), (lambda term: v[V48.at(V48.STUDENT, s, term)])
+        losses["reproj_loss/%d" % s], losses["loss/%d" % s] = v[V48.REPROJ_BOTH + s], v[V48.LOSS_BOTH + s]
+        losses["consistency_loss/%d" % s] = m(V48.CONSISTENCY)
+        losses["main/reproj_loss/%d" % s], losses["main/loss/%d" % s] = m(V48.REPROJ), m(V48.LOSS)
+        losses["smooth_loss/multi/%d" % s], mono_losses["smooth_loss/%d" % s] = m(V48.SMOOTH), t(V48.SMOOTH)
         if getattr(opt, "ensemble", False):
-            losses["ensemble_loss/%d" % s] = v[44 + s]
-        mono_losses["reproj_loss/%d" % s], mono_losses["loss/%d" % s] = v[s * 4], v[s * 4 + 3]
-    losses["main/loss"] = v[33]
+            losses["ensemble_loss/%d" % s] = v[V48.ENSEMBLE + s]
+        mono_losses["reproj_loss/%d" % s], mono_losses["loss/%d" % s] = t(V48.REPROJ), t(V48.LOSS)
+    losses["main/loss"] = v[V48.STUDENT_TOTAL]
     if want_decisions:
         return losses, mono_losses, {"dec_teacher": list(decs[:sclm + 1]), "dec_student": list(decs[sclm + 1:])}
     return losses, mono_losses
