@@ -11,6 +11,16 @@ namespace mal {
 // that a concurrent mal_set_option is a defined (if ill-advised) thing to do.  They are same-box A/B switches, not per-call
 // state: set them before the first launch (a step reads some of them in both of its calls).
 typedef std::atomic<int> opt_t;
+// the options read outside the file that defines them (mal_set_option / mal_get_option in mal_march.hip reach all of them)
+extern opt_t g_costvol_impl;                                      // mal_costvol.hip
+extern opt_t g_device_cus;                                        // mal_march.hip
+extern opt_t g_photo_impl, g_syn_rows, g_syn_queue;               // mal_photo_march.hip
+extern opt_t g_epi_bwd_planes, g_epi_probe;                       // mal_epipolar.hip
+extern opt_t g_dyn_small_blocks;                                  // mal_dyn.hip
+extern opt_t g_step_overlap, g_student_overlap, g_tail_overlap, g_sweeps_batched, g_side_priority, g_side_order, g_march_halo1,
+    g_temporal_spec;                                              // mal_step.hip
+extern opt_t g_ms_fold;                                           // mal_step_ms.hip
+extern std::atomic<hipEvent_t> g_prof_start, g_prof_stop;         // mal_api.hip: one-shot timing hooks
 
 // tile geometry of the fused / photometric kernels: 64x16 output pixels per 256-thread
 // workgroup; one wave owns one 64-pixel row segment per step, so every global access of the

@@ -21,12 +21,9 @@
 // tie-break noise, its own cotangent (g_pu_total: upstream adds the term after the division by len(scales), :337-343).
 #include "mal_march.h"
 #include "mal_device.h"
+#include "mal_tail.h"
 
 namespace mal {
-
-extern opt_t g_march_halo1;  // mal_step.hip
-int smooth_march_sweep_batch(int n, const float* const* disp, const float* const* img, int B, const int* H, const int* W,
-                             float* const* gn, double* const* partial, hipStream_t st, int* per_sample);
 
 constexpr int kDrIt = MAL_DR_MAX_ITERS;
 constexpr int kDrSlots = kDrIt + 1;  // + the pose-update pass (slot n_iters)
@@ -124,78 +121,31 @@ __global__ __launch_bounds__(256) void dr_prologue_kernel(DrPrologue p) {
 __global__ __launch_bounds__(256) void dr_final_kernel(DrFinal p) {
   __shared__ double s_part[256];
   __shared__ double s_gP[24];
-  __shared__ unsigned s_last;
   const int tid = threadIdx.x, B = p.B, HW = p.H * p.W, nB = (p.n + p.pu) * B;
   if ((int)blockIdx.x < nB) {
     const int it = blockIdx.x / B, b = blockIdx.x - it * B;
     const int j = tid & 7, sub = tid >> 3;
     double acc = 0.0;
-    if (j < 4) {
-      const double* q = p.bs[it] + (size_t)b * p.per_sample * 8 + j;
-#pragma unroll 8
-      for (int t = sub; t < p.per_sample; t += 32) acc += q[(size_t)t * 8];
-    } else if (it < p.n) {
-      const double* q = p.sm[it] + (size_t)b * p.per_sample_sm * p.sm_stride + (j - 4);
-#pragma unroll 8
-      for (int t = sub; t < p.per_sample_sm; t += 32) acc += q[(size_t)t * p.sm_stride];
-    }
-    s_part[tid] = acc;
-    __syncthreads();
-    if (tid < 8) {
-      double a = 0.0;
-      for (int k = 0; k < 32; ++k) a += s_part[k * 8 + tid];
-      p.ps[((size_t)it * B + b) * 8 + tid] = a;
-    }
+    if (j < 4) acc = tail_strided_sum(acc, p.bs[it] + (size_t)b * p.per_sample * 8 + j, 8, p.per_sample, sub);
+    else if (it < p.n)
+      acc = tail_strided_sum(acc, p.sm[it] + (size_t)b * p.per_sample_sm * p.sm_stride + (j - 4), p.sm_stride, p.per_sample_sm, sub);
+    tail_sample_sums(acc, s_part, p.ps + ((size_t)it * B + b) * 8);
   } else {
     const int i2 = blockIdx.x - nB, it = i2 / B, b = i2 - it * B;
-    const int v = tid % 24, sub = tid / 24;
-    double acc = 0.0;
-    if (sub < 10) {
-#pragma unroll 8
-      for (int t = sub; t < p.per_sample; t += 10) acc += (double)p.bgP[it][((size_t)b * p.per_sample + t) * 24 + v];
-    }
-    s_part[tid] = acc;
-    __syncthreads();
-    if (tid < 24) {
-      double a = 0.0;
-      for (int k = 0; k < 10; ++k) a += s_part[k * 24 + tid];
-      s_gP[tid] = a;
-    }
-    __syncthreads();
-    if (tid < 32) {
-      const int f = tid >> 4, e = tid & 15, k = e >> 2, j = e & 3;
-      const float* Kb = p.K + b * 16;
-      double a = 0.0;
-      for (int i = 0; i < 3; ++i) a += (double)Kb[i * 4 + k] * s_gP[f * 12 + i * 4 + j];
-      p.gT[((size_t)it * 2 + f) * B * 16 + b * 16 + e] = (float)a;
-    }
+    const double a = tail_pose_block(p.bgP[it], p.per_sample, p.K, b, s_part, s_gP);
+    if (tid < 32) p.gT[((size_t)it * 2 + (tid >> 4)) * B * 16 + b * 16 + (tid & 15)] = (float)a;
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(p.ticket, 1u);
-  __syncthreads();
-  if (s_last != gridDim.x - 1) return;
-  __threadfence();
+  if (!tail_last_workgroup(p.ticket)) return;
   // per-sample statistics of the smoothness gradient (mean and the mean-coupling term), then the scalars: thread it
-  const int HWs = p.hs * p.ws;
-  for (int s = tid; s < p.n * B; s += 256) {
-    const double* q = p.ps + (size_t)s * 8;
-    const double mean = q[7] / (double)HWs;
-    const double m = (double)((float)mean + 1e-7f);
-    p.stats[s] = mean;
-    p.stats[kDrIt * B + s] = q[6] / ((double)HWs * m * m);
-  }
+  const double hws = (double)(p.hs * p.ws);
+  for (int s = tid; s < p.n * B; s += 256) tail_smooth_stats(p.ps + (size_t)s * 8, hws, p.stats + s, p.stats + kDrIt * B + s);
   __syncthreads();
   if (tid < p.n) {
     const int it = tid;
     double tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int b = 0; b < B; ++b) {
       const double* q = p.ps + ((size_t)it * B + b) * 8;
-      for (int j = 0; j < 8; ++j) {
-        double v = q[j];
-        if (j == 4 || j == 5) v = v * (double)div_(1.0f, (float)(q[7] / (double)HWs) + 1e-7f);
-        tot[j] += v;
-      }
+      for (int j = 0; j < 8; ++j) tot[j] += tail_weighted_slot(q, j, hws);
     }
     const double N = (double)B * HW, Nx = (double)B * p.hs * (p.ws - 1), Ny = (double)B * (p.hs - 1) * p.ws;
     p.losses[it * 4 + 0] = (float)(tot[0] / (tot[1] + 1e-7));
@@ -273,7 +223,7 @@ __global__ __launch_bounds__(256) void dr_assemble_kernel(DrAssemble p) {
         const int b = row / H, y = row - b * H;
         const float* brow = bn ? march_boundary_row(bn, b, y, H, W, p.rows, p.segs) : nullptr;
         const size_t r0 = (size_t)row * W;
-        for (int x = threadIdx.x; x < W; x += 256) o2[r0 + x] = cR * (brow ? G[r0 + x] + brow[x] : G[r0 + x]);
+        for (int x = threadIdx.x; x < W; x += 256) o2[r0 + x] = cR * tail_boundary_G(G, brow, r0 + x, x);
       }
     }
     return;
@@ -284,9 +234,9 @@ __global__ __launch_bounds__(256) void dr_assemble_kernel(DrAssemble p) {
   if (lo) {  // the smoothness term of a lower scale: its own, smaller map
     for (int row = blockIdx.x; row < B * p.hs; row += gridDim.x) {
       const int b = row / p.hs;
-      const float inv = div_(1.0f, (float)p.stats[it * B + b] + 1e-7f), corr = (float)p.stats[kDrIt * B + it * B + b];
+      const float inv = tail_inv_mean(p.stats[it * B + b]), corr = (float)p.stats[kDrIt * B + it * B + b];
       const size_t r0 = (size_t)row * p.ws;
-      for (int x = threadIdx.x; x < p.ws; x += 256) lo[r0 + x] = cS * (gn[r0 + x] * inv - corr);
+      for (int x = threadIdx.x; x < p.ws; x += 256) lo[r0 + x] = tail_smooth_grad(cS, gn[r0 + x], inv, corr);
     }
   }
   if (!out) return;
@@ -297,19 +247,19 @@ __global__ __launch_bounds__(256) void dr_assemble_kernel(DrAssemble p) {
   const bool pa = p.pu_on && p.pu_into[0] == it + 1, pb = p.pu_on && p.pu_into[1] == it + 1;
   for (int row = blockIdx.x; row < B * H; row += gridDim.x) {
     const int b = row / H, y = row - b * H;
-    const float inv = div_(1.0f, (float)p.stats[it * B + b] + 1e-7f), corr = (float)p.stats[kDrIt * B + it * B + b];
+    const float inv = tail_inv_mean(p.stats[it * B + b]), corr = (float)p.stats[kDrIt * B + it * B + b];
     const float* brow = p.bnd[it] ? march_boundary_row(p.bnd[it], b, y, H, W, p.rows, p.segs) : nullptr;
     const float* browA = (pa && p.bnd[p.n]) ? march_boundary_row(p.bnd[p.n], b, y, H, W, p.rows, p.segs) : nullptr;
     const float* browB = (pb && p.bnd2) ? march_boundary_row(p.bnd2, b, y, H, W, p.rows, p.segs) : nullptr;
     const size_t r0 = (size_t)row * W;
     for (int x = threadIdx.x; x < W; x += 256) {
       const size_t i = r0 + x;
-      const float G = brow ? G_r[i] + brow[x] : G_r[i];
-      float v = with_smooth ? cS * (gn[i] * inv - corr) : 0.f;
+      const float G = tail_boundary_G(G_r, brow, i, x);
+      float v = with_smooth ? tail_smooth_grad(cS, gn[i], inv, corr) : 0.f;
       if (G_c) v = fma_(cC, G_c[i], v);
       v = fma_(cR, G, v);
-      if (pa) v = fma_(cP, browA ? p.G_r[p.n][i] + browA[x] : p.G_r[p.n][i], v);
-      if (pb) v = fma_(cP, browB ? p.G_r2[i] + browB[x] : p.G_r2[i], v);
+      if (pa) v = fma_(cP, tail_boundary_G(p.G_r[p.n], browA, i, x), v);
+      if (pb) v = fma_(cP, tail_boundary_G(p.G_r2, browB, i, x), v);
       out[i] = v;
     }
   }

@@ -174,6 +174,24 @@ struct FusedMoreArgs {
   size_t orig_stride; int weight_given;
 };
 int photo_march_fused_more_n(int n, const FusedMoreArgs* a, int B, int H, int W, int* per_sample_out, hipStream_t st);
+// mal_photo_march.hip: one such sweep (the arguments are FusedMoreArgs' + the task order of a region-gated sweep); the batched
+// edge-aware smoothness sweep over n <= 8 maps (per_sample[k]: tasks per sample of map k) and its tasks per sample of one map
+int photo_march_fused_more(const float* target, const float* cand0, const float* cand1, int idx0, const float* ident,
+                           const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H, int W,
+                           float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
+                           float* g_cand1, int* per_sample_out, hipStream_t st, const uint8_t* region, float* g_region0,
+                           float* g_region1, unsigned* order, unsigned* order_count, const float* orig0, const float* orig1,
+                           size_t orig_stride, int target_texels, int weight_given);
+int smooth_march_sweep_batch(int n, const float* const* disp, const float* const* img, int B, const int* H, const int* W,
+                             float* const* gn, double* const* partial, hipStream_t st, int* per_sample);
+int smooth_march_batch_tasks(int H, int W);
+// mal_step.hip: the library's side stream of the caller's stream (fork / join through events: capturable) and the launch of
+// n <= 4 tie-break noise maps
+hipStream_t side_begin(hipStream_t st);
+int side_end(hipStream_t st);
+int side_wait(hipStream_t st, bool always);
+int tiebreak_noise_launch(unsigned long long seed, unsigned long long step, const unsigned long long* counter, unsigned mult,
+                          int n, int B, int H, int W, float* const* out, hipStream_t st);
 // The four-scale step (mal_step_ms.hip): its per-scale tie-break noise maps (MAL_STEP_NOISE_PHILOX) and the bilinear
 // upsampling of the lower scales' disparities to full resolution (trainer.py:1094-1096) -- neither reads anything the
 // identity / packing sweep writes -- as extra workgroups of that sweep's launch instead of two launches behind it.

@@ -37,8 +37,6 @@
 
 namespace mal {
 
-extern std::atomic<hipEvent_t> g_prof_start, g_prof_stop;
-
 // -DMAL_STAGE_MARKS (scripts/valu_budget.py): stage boundaries of the row loop as labelled comments in the compiler's
 // listing, each behind a scheduling barrier so that no instruction crosses one -- the per-stage instruction budget of
 // profiles/r04_valu_budget.json.  The shipped build has neither the comments nor the barriers.
@@ -1619,7 +1617,6 @@ __global__ __launch_bounds__(64, 3) void pack_identity_kernel(IdentParams p) {
 }
 
 opt_t g_pass_impl{1};   // 1 = marching (this file, fastest); 0 = LDS-tiled v1 (mal_pass.hip); 2 = LDS-tiled, 512 threads (mal_tile2.hip)
-extern opt_t g_costvol_impl;  // mal_costvol.hip
 opt_t g_march_flip{1};  // odd segments bottom-up (mal_set_option("march_flip", 0|1))
 opt_t g_march_rows{0};  // output rows per wave task; 0 = pick so that one round of tasks fills the chip
 opt_t g_pack_rows{10};  // rows per task of the identity / packing sweep: 20 segments x 11 strips x 12 samples = 2640 tasks <= 3072 (three waves per SIMD); same-box steps, round 3: 10: 0.2010 / 0.3270 ms (--distil / headline), 9: 0.2019 / 0.3290, 11: 0.2043 / 0.3291, 12: 0.329 (headline)
@@ -1627,21 +1624,6 @@ opt_t g_march_rows_fwd{0};  // the same for the forward-only passes (<= 168 VGPR
 opt_t g_device_cus{0};  // option "device_cus": decompose as if the device had this many CUs (0 = ask the device)
 opt_t g_debug{0};
 std::atomic<unsigned*> g_dec_next{nullptr};  // mal_decisions_next_pass (one-shot, taken with an atomic exchange): decision planes for the next instrumentable gradient pass
-extern opt_t g_photo_impl;  // mal_photo_march.hip
-extern opt_t g_epi_bwd_planes;  // mal_epipolar.hip
-extern opt_t g_epi_probe;       // mal_epipolar.hip
-extern opt_t g_syn_rows;        // mal_photo_march.hip
-extern opt_t g_syn_queue;       // mal_photo_march.hip
-extern opt_t g_step_overlap;    // mal_step.hip
-extern opt_t g_student_overlap; // mal_step.hip
-extern opt_t g_tail_overlap;    // mal_step.hip
-extern opt_t g_sweeps_batched;  // mal_step.hip
-extern opt_t g_ms_fold;         // mal_step_ms.hip
-extern opt_t g_dyn_small_blocks; // mal_dyn.hip
-extern opt_t g_side_priority;   // mal_step.hip
-extern opt_t g_side_order;      // mal_step.hip
-extern opt_t g_march_halo1;     // mal_step.hip
-extern opt_t g_temporal_spec;   // mal_step.hip
 opt_t g_march_lean{1};         // option "march_lean": the teacher's passes without the optional operands' code (0: generic, A/B)
 opt_t g_march3{0};             // option "march3": the teacher's gradient pass as a three-wave pipeline (0: one wave per strip)
 

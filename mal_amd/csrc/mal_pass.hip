@@ -30,10 +30,9 @@
 #include "mal_common.h"
 #include <atomic>
 #include "mal_device.h"
+#include "mal_tail.h"
 
 namespace mal {
-
-extern std::atomic<hipEvent_t> g_prof_start, g_prof_stop;  // mal_api.hip: one-shot timing hooks
 
 #ifdef MAL_EXPERIMENTS  // the LDS-tiled first formulation (option "pass_impl" 0): not in the default build
 #include "experiments/pass_tiled.inc"
@@ -49,12 +48,7 @@ __global__ __launch_bounds__(256) void pass_finalize_kernel(const double* block_
   const int tid = threadIdx.x;
   if (fold.bnd && (int)blockIdx.x >= fold_first) {
     // one-row halo of the marching gradient pass: add the neighbouring task's scratch row to a segment's first / last row
-    const int i = blockIdx.x - fold_first, which = i & 1, bs = i >> 1, seg = bs % fold.segs, b = bs / fold.segs;
-    if ((which == 0 && seg == 0) || (which == 1 && seg == fold.segs - 1)) return;
-    const int y = which == 0 ? seg * fold.rows : min(seg * fold.rows + fold.rows, fold.H) - 1;
-    float* g = fold.g + ((size_t)b * fold.H + y) * fold.W;
-    const float* r = fold.bnd + ((size_t)(b * fold.segs + seg) * 2 + which) * fold.W;
-    for (int x = tid; x < fold.W; x += 256) g[x] += r[x];
+    tail_fold_boundary_row(fold.g, fold.bnd, (int)blockIdx.x - fold_first, fold.H, fold.W, fold.rows, fold.segs);
     return;
   }
   if (blockIdx.x < 8) {

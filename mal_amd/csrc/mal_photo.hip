@@ -14,6 +14,7 @@
 // LDS-tiled, single-launch formulation of the same arithmetic is mal_pass.hip.
 #include "mal_common.h"
 #include "mal_device.h"
+#include "mal_tail.h"
 
 namespace mal {
 
@@ -161,7 +162,6 @@ __global__ __launch_bounds__(256) void reproj_bwd_kernel(const float* pred, cons
 
 // ---------------------------------------------------------------- photo fwd / bwd
 // marching formulation (mal_photo_march.hip), the default for SSIM + min
-extern opt_t g_photo_impl;
 int photo_march_fwd(const float* target, const float* const* cand, int n_cand, const float* ident, const float* noise,
                     const float* ext_mask, int B, int H, int W, int automask, float* min_reproj, uint8_t* argmin,
                     float* weight_out, double* block_sums, int* ntasks_out, hipStream_t st);
@@ -324,10 +324,7 @@ __global__ __launch_bounds__(64) void smooth_mid_kernel(SmoothParams p, int stag
     double dot = 0.0;
     for (int k = lane; k < p.chunks; k += 64) dot += p.partial[(size_t)(b * p.chunks + k) * 4 + 2];
     dot = wave_sum_d(dot);
-    if (lane == 0) {
-      const double m = (double)((float)p.stats[b] + 1e-7f);
-      p.stats[p.B + b] = dot / ((double)HW * m * m);
-    }
+    if (lane == 0) p.stats[p.B + b] = tail_smooth_corr(dot, p.stats[b], (double)HW);
   } else {
     double sx = 0.0, sy = 0.0;
     for (int i = lane; i < p.B * p.chunks; i += 64) { sx += p.partial[(size_t)i * 4]; sy += p.partial[(size_t)i * 4 + 1]; }

@@ -676,7 +676,6 @@ int smooth_march(const float* disp, const float* img, int B, int H, int W, int n
 
 opt_t g_photo_impl{1};  // 1 = marching kernels of this file; 0 = one-pixel-per-thread kernels of mal_photo.hip
 
-extern opt_t g_device_cus;  // mal_march.hip: option "device_cus" (> 0: the CU count to decompose for, no device query)
 static int device_slots() {
   if (g_device_cus > 0) return g_device_cus * 4;
   static int slots = 0;

@@ -19,17 +19,10 @@
 #include "mal_device.h"
 #include "mal_pose.h"
 #include "mal_pairs.h"
+#include "mal_tail.h"
 #include <mutex>
 
 namespace mal {
-
-// mal_photo_march.hip: the materialised-candidate kernels (the two synthesised images of the temporal hint)
-int photo_march_fused_more(const float* target, const float* cand0, const float* cand1, int idx0, const float* ident,
-                           const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H, int W,
-                           float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
-                           float* g_cand1, int* per_sample_out, hipStream_t st, const uint8_t* region, float* g_region0,
-                           float* g_region1, unsigned* order, unsigned* order_count, const float* orig0, const float* orig1,
-                           size_t orig_stride, int target_texels, int weight_given);
 
 constexpr int kLossSlots = 16;
 constexpr int kEpiBlocks = 64;  // epilogue workgroups per sample in the final launch (their partials are summed in block order)
@@ -242,139 +235,51 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(EpiParams p) { step_
 // and the block that finishes last (a ticket counter, reset by the step's first launch) turns the per-sample sums into the smoothness of the mean-normalised disparities (layers.py:210-223,
 // loss_utils.py:119-121), the loss scalars (loss_utils.py:112-127,198-279; trainer.py:625-629) and the
 // coefficients of the backward.
-__global__ __launch_bounds__(256) void step_final_kernel(const double* bs_t, const double* bs_s, const float* bgP,
-                                                         const double* bs_p, int per_sample_p,
-                                                         const double* bs_ph, int per_sample_ph, const double* bs_sh,
-                                                         int per_sample_sh, const double* bs_d,
-                                                         const float* K, int per_sample, int per_sample_t, int B, int H, int W,
-                                                         float w_main, float w_distil, double* ps, float* gT0, float* gT1,
-                                                         double* stats, float* losses, float* coefs, float* loss_total,
-                                                         unsigned* ticket, unsigned long long* noise_counter) {
+struct StepFinal {
+  const double* bs_t; const double* bs_s; const float* bgP;  // bgP null (temporal hint): no pose workgroups in this launch
+  const double* bs_p; int per_sample_p;
+  // temporal hint: the teacher's sums are those of the pass in front of the producer (bs_t, its own decomposition:
+  // per_sample_t tasks) plus the fused sweep's per-task differences bs_ph ([task][2]); --main_temporal: the student's likewise
+  const double* bs_ph; int per_sample_ph; const double* bs_sh; int per_sample_sh;
+  const double* bs_d;  // the student's consistency / distillation sums as step_epilogue_kernel's per-block partials (nullable)
+  const float* K; int per_sample, per_sample_t, B, H, W;
+  float w_main, w_distil;
+  double* ps; float* gT0; float* gT1; double* stats; float* losses; float* coefs; float* loss_total; unsigned* ticket;
+  unsigned long long* noise_counter;
+};
+__global__ __launch_bounds__(256) void step_final_kernel(StepFinal p) {
   __shared__ double s_part[256];
   __shared__ double s_gP[24];
   __shared__ double sh_tot[2][8];
-  __shared__ unsigned s_last;
-  const int tid = threadIdx.x, HW = H * W;
+  const int tid = threadIdx.x, B = p.B, H = p.H, W = p.W, HW = H * W;
   const int bid = (int)blockIdx.x;
   if (bid < 2 * B) {
     const int pass = bid / B, b = bid - pass * B;
     const int j = tid & 7, sub = tid >> 3;  // 32 strided partial sums per quantity
-    // temporal hint: the teacher's sum(rp*w), sum(w) come from the materialised-candidate kernel ([task][2])
-    // temporal hint: the teacher's sums are those of the pass in front of the producer (bs_t, its own decomposition:
-    // per_sample_t tasks) plus the fused sweep's per-task differences ([task][2])
-    const bool ph = pass == 0 && bs_ph != nullptr;
-    const int ps_pass = pass ? per_sample : per_sample_t;
-    const double* bs = j < 4 ? (pass ? bs_s : bs_t) + (size_t)b * ps_pass * 8 + j
-                             : bs_p + (size_t)b * per_sample_p * 8 + pass * 4 + (j - 4);
-    const int n_t = j < 4 ? ps_pass : per_sample_p;
+    const int ps_pass = pass ? p.per_sample : p.per_sample_t;
+    // (the wave's eight slots walk their sources in ONE loop: pointer and count are selected, not the loop)
+    const double* bs = j < 4 ? (pass ? p.bs_s : p.bs_t) + (size_t)b * ps_pass * 8 + j
+                             : p.bs_p + (size_t)b * p.per_sample_p * 8 + pass * 4 + (j - 4);
+    const int n_t = j < 4 ? ps_pass : p.per_sample_p;
     double acc = 0.0;
-    if (bs_d && pass == 1 && (j == 2 || j == 3)) {
-      // the consistency / distillation sums of the student come from step_epilogue_kernel's per-block partials (block order)
-      const double* bd = bs_d + (size_t)b * kEpiBlocks * 2 + (j - 2);
-#pragma unroll 8
-      for (int t = sub; t < kEpiBlocks; t += 32) acc += bd[(size_t)t * 2];
-    } else {
-#pragma unroll 8
-    for (int t = sub; t < n_t; t += 32) acc += bs[(size_t)t * 8];  // independent loads: issue them together
-    }
-    if (ph && j < 2) {
-      const double* bd = bs_ph + (size_t)b * per_sample_ph * 2 + j;
-#pragma unroll 8
-      for (int t = sub; t < per_sample_ph; t += 32) acc += bd[(size_t)t * 2];
-    }
-    if (pass == 1 && bs_sh != nullptr && j < 2) {  // --main_temporal: the student's sums likewise
-      const double* bd = bs_sh + (size_t)b * per_sample_sh * 2 + j;
-#pragma unroll 8
-      for (int t = sub; t < per_sample_sh; t += 32) acc += bd[(size_t)t * 2];
-    }
-    s_part[tid] = acc;
-    __syncthreads();
-    if (tid < 8) {
-      double a = 0.0;
-      for (int k = 0; k < 32; ++k) a += s_part[k * 8 + tid];
-      ps[((size_t)pass * B + b) * 8 + tid] = a;
-    }
-  } else if (bgP != nullptr) {
+    if (p.bs_d && pass == 1 && (j == 2 || j == 3))  // (block order)
+      acc = tail_strided_sum(acc, p.bs_d + (size_t)b * kEpiBlocks * 2 + (j - 2), 2, kEpiBlocks, sub);
+    else acc = tail_strided_sum(acc, bs, 8, n_t, sub);
+    if (pass == 0 && p.bs_ph && j < 2) acc = tail_strided_sum(acc, p.bs_ph + (size_t)b * p.per_sample_ph * 2 + j, 2, p.per_sample_ph, sub);
+    if (pass == 1 && p.bs_sh && j < 2) acc = tail_strided_sum(acc, p.bs_sh + (size_t)b * p.per_sample_sh * 2 + j, 2, p.per_sample_sh, sub);
+    tail_sample_sums(acc, s_part, p.ps + ((size_t)pass * B + b) * 8);
+  } else if (p.bgP != nullptr) {
     const int b = bid - 2 * B;
-    // 24 sums of per_sample partials: 10 threads per value (240 of 256), then a 10-term sum (fixed order)
-    const int v = tid % 24, sub = tid / 24;
-    double acc = 0.0;
-    if (sub < 10) {
-#pragma unroll 8
-      for (int t = sub; t < per_sample_t; t += 10) acc += (double)bgP[((size_t)b * per_sample_t + t) * 24 + v];  // the teacher's gradient pass
-    }
-    s_part[tid] = acc;
-    __syncthreads();
-    if (tid < 24) {
-      double a = 0.0;
-      for (int k = 0; k < 10; ++k) a += s_part[k * 24 + tid];
-      s_gP[tid] = a;
-    }
-    __syncthreads();
-    if (tid < 32) {
-      const int f = tid >> 4, e = tid & 15, k = e >> 2, j = e & 3;
-      const float* Kb = K + b * 16;
-      double a = 0.0;
-      for (int i = 0; i < 3; ++i) a += (double)Kb[i * 4 + k] * s_gP[f * 12 + i * 4 + j];
-      (f ? gT1 : gT0)[b * 16 + e] = (float)a;
-    }
+    const double a = tail_pose_block(p.bgP, p.per_sample_t, p.K, b, s_part, s_gP);  // the teacher's gradient pass
+    if (tid < 32) ((tid >> 4) ? p.gT1 : p.gT0)[b * 16 + (tid & 15)] = (float)a;
   }
-  // ---- the last block to get here does the scalar epilogue.  Publishing relies on this order: (1) the workgroup barrier --
-  // __syncthreads() is a workgroup-scope release/acquire, so every thread's stores above happen-before lane 0's fence (barrier
-  // cumulativity); (2) ONE agent-scope release fence by lane 0 (an L2 write-back: cheap once per workgroup, 40 us when all 256
-  // threads of 768 workgroups issued a __threadfence() each); (3) the ticket atomic; (4) an agent-scope acquire in the one
-  // workgroup that continues.
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    s_last = atomicAdd(ticket, 1u);
-  }
-  __syncthreads();
-  if (s_last != gridDim.x - 1) return;
-  __threadfence();  // (the one workgroup that continues: acquire what the others published)
-  // sums over samples, fixed order; slots 4, 5 (smoothness) are weighted by the sample's 1/(mean+1e-7).  One
-  // thread per (pass, sample, slot) fetches and weighs its term (a single round trip for all of them), 16 threads
-  // then add the B terms in sample order.
-  constexpr int kMaxStepB = 64;  // beyond this the terms are re-fetched by the summing threads instead of staged in LDS
-  __shared__ double s_term[2 * kMaxStepB * 8];
-  const bool staged = B <= kMaxStepB;
-  for (int i = tid; staged && i < 2 * B * 8; i += 256) {
-    const int j = i & 7;
-    const double* q = ps + (size_t)(i >> 3) * 8;
-    double v = q[j];
-    if (j == 4 || j == 5) {
-      const float m = (float)(q[7] / (double)HW) + 1e-7f;
-      v = v * (double)div_(1.0f, m);
-    }
-    s_term[i] = v;
-  }
-  // per-sample statistics of the smoothness gradient: mean and the mean-coupling term dot/(HW (mean+eps)^2)
-  for (int s = tid; s < 2 * B; s += 256) {
-    const double* q = ps + (size_t)s * 8;
-    const double mean = q[7] / (double)HW;
-    const double m = (double)((float)mean + 1e-7f);
-    stats[s] = mean;
-    stats[2 * B + s] = q[6] / ((double)HW * m * m);
-  }
-  __syncthreads();
-  if (tid < 16) {
-    const int pass = tid >> 3, j = tid & 7;
-    double a = 0.0;
-    for (int b = 0; b < B; ++b) {
-      double v;
-      if (staged) v = s_term[((size_t)pass * B + b) * 8 + j];
-      else {
-        const double* q = ps + ((size_t)pass * B + b) * 8;
-        v = q[j];
-        if (j == 4 || j == 5) v = v * (double)div_(1.0f, (float)(q[7] / (double)HW) + 1e-7f);
-      }
-      a += v;
-    }
-    sh_tot[pass][j] = a;
-  }
-  __syncthreads();
+  if (!tail_last_workgroup(p.ticket)) return;
+  // the scalar epilogue: sums over samples, per-sample statistics of the smoothness gradient
+  tail_sum_over_samples(p.ps, 2, 1, B, H, W, p.stats, sh_tot);
   if (tid != 0) return;
-  if (noise_counter) *noise_counter += 1ull;  // every kernel of this step that reads it has finished (stream order)
+  if (p.noise_counter) *p.noise_counter += 1ull;  // every kernel of this step that reads it has finished (stream order)
+  const float w_main = p.w_main, w_distil = p.w_distil;
+  float* losses = p.losses; float* coefs = p.coefs;
   const double* st = sh_tot[0];
   const double* ss = sh_tot[1];
   const double N = (double)B * HW, Nx = (double)B * H * (W - 1), Ny = (double)B * (H - 1) * W;
@@ -387,7 +292,7 @@ __global__ __launch_bounds__(256) void step_final_kernel(const double* bs_t, con
   losses[3] = (float)reproj_s; losses[4] = (float)cons; losses[5] = (float)smooth_s; losses[6] = (float)distil;
   losses[7] = loss_m;
   losses[8] = w_main * (loss_m + loss_t) + w_distil * (float)distil;
-  if (loss_total) *loss_total = losses[8];
+  if (p.loss_total) *p.loss_total = losses[8];
   losses[9] = (float)reproj_s + (float)reproj_t;            // "reproj_loss/0" after the mono losses are added in
   losses[10] = (loss_m + (float)distil) + loss_t;           // "loss/0" / "loss" without loss balancing
   losses[11] = loss_m + loss_t;                             // loss_list[0] with loss balancing
@@ -402,75 +307,64 @@ __global__ __launch_bounds__(256) void step_final_kernel(const double* bs_t, con
 // d total / d disp for both maps; block 0 also scales the pose gradients and runs the backward of
 // transformation_from_parameters (pp.gT = the scaled gradients, pp.g_axisangle / g_translation nullable).  With the
 // temporal hint (bgP != nullptr) the first B workgroups reduce their sample's pose partials first.
-__global__ __launch_bounds__(256) void step_assemble_kernel(const float* G_r_t, const float* G_r_s, const float* G_cd,
-                                                            const float* gn_t, const float* gn_s,
-                                                            const float* coefs, const double* stats, const float* g_total,
-                                                            int B, int HW, const float* gT0, const float* gT1,
-                                                            float* gTs0, float* gTs1, float* g_disp_t, float* g_disp_s,
-                                                            PoseParams pp, int pose_bwd, const float* bgP, const float* K,
-                                                            int per_sample, int W, const float* bnd_t, const float* bnd_s,
-                                                            int rows, int segs, float* fix_t, const float* G_e, float* g_ens,
-                                                            const float* G_dual, int parts) {
+struct StepAssemble {
+  const float* G_r_t; const float* G_r_s; const float* G_cd; const float* gn_t; const float* gn_s;
+  const float* coefs; const double* stats; const float* g_total;
+  int B, HW, W;
+  const float* gT0; const float* gT1; float* gTs0; float* gTs1; float* g_disp_t; float* g_disp_s;
+  int pose_bwd;
+  const float* bgP; const float* K; int per_sample;  // temporal hint: the teacher's pose partials are still per task
+  const float* bnd_t; const float* bnd_s; int rows, segs;  // boundary scratch rows of the two gradient passes (nullable)
+  float* fix_t;         // temporal hint: the teacher's sweep finished its own rows, the neighbour's term is added here
+  const float* G_e; float* g_ens;  // --learn_ens
+  const float* G_dual;  // --dual_distil
+  int parts;
+};
+__global__ __launch_bounds__(256) void step_assemble_kernel(StepAssemble p, PoseParams pp) {
   // parts (option "tail_overlap": the student's half is launched while the teacher's sweep still runs, the rest behind it):
   // bit 0 = the teacher's map, bit 1 = the student's map (and the ensemble head's), bit 2 = the pose gradients; 7 = everything
-  const float g = g_total ? *g_total : 1.0f;
-  const float cRt = coefs[0] * g, cRs = coefs[1] * g, cS = coefs[4] * g;  // coefs[2], [3] are already inside G_cd
-  if (!(parts & 1)) { g_disp_t = nullptr; fix_t = nullptr; }
-  if (!(parts & 2)) { g_disp_s = nullptr; g_ens = nullptr; }
-  if (!(parts & 4)) {
+  const int B = p.B, W = p.W;
+  const float g = p.g_total ? *p.g_total : 1.0f;
+  const float cRt = p.coefs[0] * g, cRs = p.coefs[1] * g, cS = p.coefs[4] * g;  // coefs[2], [3] are already inside G_cd
+  float* g_disp_t = (p.parts & 1) ? p.g_disp_t : nullptr;
+  float* fix_t = (p.parts & 1) ? p.fix_t : nullptr;
+  float* g_disp_s = (p.parts & 2) ? p.g_disp_s : nullptr;
+  float* g_ens = (p.parts & 2) ? p.g_ens : nullptr;
+  const float *G_r_t = p.G_r_t, *G_r_s = p.G_r_s, *G_cd = p.G_cd, *gn_t = p.gn_t, *gn_s = p.gn_s, *G_dual = p.G_dual;
+  if (!(p.parts & 4)) {
     // (no pose work in this launch)
-  } else if (bgP) {
-    // temporal hint: the teacher's sweep ran in this backward call, its pose partials are still per task: workgroup b
-    // reduces sample b's (step_final_kernel's pose branch), scales and runs that sample's pose backward
+  } else if (p.bgP) {
+    // workgroup b reduces sample b's pose partials (tail_pose_block, as step_final_kernel does without the hint), scales and
+    // runs that sample's pose backward
     if ((int)blockIdx.x < B) {
       __shared__ double s_part[256];
       __shared__ double s_gP[24];
       const int tid = threadIdx.x, b = blockIdx.x;
-      const int v = tid % 24, sub = tid / 24;
-      double acc = 0.0;
-      if (sub < 10) {
-#pragma unroll 8
-        for (int t = sub; t < per_sample; t += 10) acc += (double)bgP[((size_t)b * per_sample + t) * 24 + v];
-      }
-      s_part[tid] = acc;
+      const double a = tail_pose_block(p.bgP, p.per_sample, p.K, b, s_part, s_gP);
+      if (tid < 32) ((tid >> 4) ? p.gTs1 : p.gTs0)[b * 16 + (tid & 15)] = (float)a * cRt;
       __syncthreads();
-      if (tid < 24) {
-        double a = 0.0;
-        for (int k = 0; k < 10; ++k) a += s_part[k * 24 + tid];
-        s_gP[tid] = a;
-      }
-      __syncthreads();
-      if (tid < 32) {
-        const int f = tid >> 4, e = tid & 15, k = e >> 2, j = e & 3;
-        const float* Kb = K + b * 16;
-        double a = 0.0;
-        for (int i = 0; i < 3; ++i) a += (double)Kb[i * 4 + k] * s_gP[f * 12 + i * 4 + j];
-        (f ? gTs1 : gTs0)[b * 16 + e] = (float)a * cRt;
-      }
-      __syncthreads();
-      if (pose_bwd && tid < 2) pose_bwd_one(pp, tid, b);
+      if (p.pose_bwd && tid < 2) pose_bwd_one(pp, tid, b);
     }
   } else if (blockIdx.x == 0) {
-    for (int i = threadIdx.x; i < B * 16; i += 256) { gTs0[i] = gT0[i] * cRt; gTs1[i] = gT1[i] * cRt; }
+    for (int i = threadIdx.x; i < B * 16; i += 256) { p.gTs0[i] = p.gT0[i] * cRt; p.gTs1[i] = p.gT1[i] * cRt; }
     __syncthreads();
-    if (pose_bwd)
+    if (p.pose_bwd)
       for (int i = threadIdx.x; i < B * 2; i += 256) pose_bwd_one(pp, i / B, i % B);
   }
   // one image row per workgroup round: the row index is wave-uniform, so is the test for a segment boundary whose
   // gradient is completed by the neighbouring task's scratch row (one-row halo of the marching passes)
-  const int H = HW / W;
+  const int H = p.HW / W;
   const bool vec4 = (W & 3) == 0;  // rows are then 16-byte aligned in every map
   for (int row = blockIdx.x; row < B * H; row += gridDim.x) {
     const int b = row / H, y = row - b * H;
-    const float inv_t = div_(1.0f, (float)stats[b] + 1e-7f), inv_s = div_(1.0f, (float)stats[B + b] + 1e-7f);
-    const float corr_t = (float)stats[2 * B + b], corr_s = (float)stats[3 * B + b];
-    const float* brow_t = bnd_t ? march_boundary_row(bnd_t, b, y, H, W, rows, segs) : nullptr;
-    const float* brow_s = bnd_s ? march_boundary_row(bnd_s, b, y, H, W, rows, segs) : nullptr;
+    const float inv_t = tail_inv_mean(p.stats[b]), inv_s = tail_inv_mean(p.stats[B + b]);
+    const float corr_t = (float)p.stats[2 * B + b], corr_s = (float)p.stats[3 * B + b];
+    const float* brow_t = p.bnd_t ? march_boundary_row(p.bnd_t, b, y, H, W, p.rows, p.segs) : nullptr;
+    const float* brow_s = p.bnd_s ? march_boundary_row(p.bnd_s, b, y, H, W, p.rows, p.segs) : nullptr;
     const size_t r0 = (size_t)row * W;
     auto px = [&](size_t i, int x) {
       if (g_disp_t) {
-        const float G = brow_t ? G_r_t[i] + brow_t[x] : G_r_t[i];
-        float v = fma_(cRt, G, cS * (gn_t[i] * inv_t - corr_t));
+        float v = fma_(cRt, tail_boundary_G(G_r_t, brow_t, i, x), tail_smooth_grad(cS, gn_t[i], inv_t, corr_t));
         if (G_dual) v += g * G_dual[i];  // --dual_distil: what the distillation term sends to the teacher's disparity
         g_disp_t[i] = v;
       } else if (fix_t && (brow_t || G_dual)) {  // the teacher's sweep finished its own rows (temporal hint): add the neighbour's term
@@ -478,11 +372,9 @@ __global__ __launch_bounds__(256) void step_assemble_kernel(const float* G_r_t, 
         if (G_dual) v += g * G_dual[i];
         if (v != 0.f) fix_t[i] = fix_t[i] + v;
       }
-      if (g_disp_s) {
-        const float G = brow_s ? G_r_s[i] + brow_s[x] : G_r_s[i];
-        g_disp_s[i] = fma_(cRs, G, fma_(g, G_cd[i], cS * (gn_s[i] * inv_s - corr_s)));
-      }
-      if (g_ens) g_ens[i] = g * G_e[i];  // --learn_ens: the loss weight is inside G_e already
+      if (g_disp_s)
+        g_disp_s[i] = fma_(cRs, tail_boundary_G(G_r_s, brow_s, i, x), fma_(g, G_cd[i], tail_smooth_grad(cS, gn_s[i], inv_s, corr_s)));
+      if (g_ens) g_ens[i] = g * p.G_e[i];  // --learn_ens: the loss weight is inside G_e already
     };
     if (vec4 && !brow_t && !brow_s && !g_ens && !G_dual) {
       // four pixels per thread, 16-byte accesses (no boundary row here: the arithmetic per element is px()'s)
@@ -491,16 +383,16 @@ __global__ __launch_bounds__(256) void step_assemble_kernel(const float* G_r_t, 
         if (g_disp_t) {
           const float4 G = *reinterpret_cast<const float4*>(G_r_t + i), n = *reinterpret_cast<const float4*>(gn_t + i);
           float4 o;
-          o.x = fma_(cRt, G.x, cS * (n.x * inv_t - corr_t)); o.y = fma_(cRt, G.y, cS * (n.y * inv_t - corr_t));
-          o.z = fma_(cRt, G.z, cS * (n.z * inv_t - corr_t)); o.w = fma_(cRt, G.w, cS * (n.w * inv_t - corr_t));
+          o.x = fma_(cRt, G.x, tail_smooth_grad(cS, n.x, inv_t, corr_t)); o.y = fma_(cRt, G.y, tail_smooth_grad(cS, n.y, inv_t, corr_t));
+          o.z = fma_(cRt, G.z, tail_smooth_grad(cS, n.z, inv_t, corr_t)); o.w = fma_(cRt, G.w, tail_smooth_grad(cS, n.w, inv_t, corr_t));
           *reinterpret_cast<float4*>(g_disp_t + i) = o;
         }
         if (g_disp_s) {
           const float4 G = *reinterpret_cast<const float4*>(G_r_s + i), n = *reinterpret_cast<const float4*>(gn_s + i);
           const float4 c = *reinterpret_cast<const float4*>(G_cd + i);
           float4 o;
-          o.x = fma_(cRs, G.x, fma_(g, c.x, cS * (n.x * inv_s - corr_s))); o.y = fma_(cRs, G.y, fma_(g, c.y, cS * (n.y * inv_s - corr_s)));
-          o.z = fma_(cRs, G.z, fma_(g, c.z, cS * (n.z * inv_s - corr_s))); o.w = fma_(cRs, G.w, fma_(g, c.w, cS * (n.w * inv_s - corr_s)));
+          o.x = fma_(cRs, G.x, fma_(g, c.x, tail_smooth_grad(cS, n.x, inv_s, corr_s))); o.y = fma_(cRs, G.y, fma_(g, c.y, tail_smooth_grad(cS, n.y, inv_s, corr_s)));
+          o.z = fma_(cRs, G.z, fma_(g, c.z, tail_smooth_grad(cS, n.z, inv_s, corr_s))); o.w = fma_(cRs, G.w, fma_(g, c.w, tail_smooth_grad(cS, n.w, inv_s, corr_s)));
           *reinterpret_cast<float4*>(g_disp_s + i) = o;
         }
       }
@@ -1149,12 +1041,18 @@ extern "C" int mal_loss_step_fwd(const mal_step_args* a) {
     if (rc) return rc;
   }
   // per-sample sums of both gradient passes, pose gradients (temporal: in _bwd, after the teacher's sweep), scalars
-  hipLaunchKernelGGL(step_final_kernel, dim3(temporal ? 2 * B : 3 * B), dim3(256), 0, st, w.bs_t, w.bs_s, temporal ? nullptr : w.bgP,
-                     w.bs_p, per_sample_p, temporal ? w.bs_ph : nullptr, per_sample_ph, main_t ? w.bs_sh : nullptr, per_sample_sh,
-                     stu_deferred ? w.bs_d : nullptr, a->K,
-                     per_sample, per_sample_t, B, H, W,
-                     a->w_main, a->w_distil, w.ps, w.gT[0], w.gT[1], w.sm_stats, a->losses, w.coefs, a->loss_total,
-                     w.ticket, (a->flags & MAL_STEP_NOISE_PHILOX) ? (unsigned long long*)a->noise_counter : nullptr);
+  StepFinal fin = {};
+  fin.bs_t = w.bs_t; fin.bs_s = w.bs_s; fin.bgP = temporal ? nullptr : w.bgP;
+  fin.bs_p = w.bs_p; fin.per_sample_p = per_sample_p;
+  fin.bs_ph = temporal ? w.bs_ph : nullptr; fin.per_sample_ph = per_sample_ph;
+  fin.bs_sh = main_t ? w.bs_sh : nullptr; fin.per_sample_sh = per_sample_sh;
+  fin.bs_d = stu_deferred ? w.bs_d : nullptr;
+  fin.K = a->K; fin.per_sample = per_sample; fin.per_sample_t = per_sample_t; fin.B = B; fin.H = H; fin.W = W;
+  fin.w_main = a->w_main; fin.w_distil = a->w_distil;
+  fin.ps = w.ps; fin.gT0 = w.gT[0]; fin.gT1 = w.gT[1]; fin.stats = w.sm_stats; fin.losses = a->losses; fin.coefs = w.coefs;
+  fin.loss_total = a->loss_total; fin.ticket = w.ticket;
+  fin.noise_counter = (a->flags & MAL_STEP_NOISE_PHILOX) ? (unsigned long long*)a->noise_counter : nullptr;
+  hipLaunchKernelGGL(step_final_kernel, dim3(temporal ? 2 * B : 3 * B), dim3(256), 0, st, fin);
   return launch_status();
 }
 
@@ -1241,14 +1139,20 @@ extern "C" int mal_loss_step_bwd(const mal_step_args* a) {
   pp.gT[0] = w.gTs[0]; pp.gT[1] = w.gTs[1];
   pp.g_axisangle[0] = a->g_axisangle_m1; pp.g_axisangle[1] = a->g_axisangle_p1;
   pp.g_translation[0] = a->g_translation_m1; pp.g_translation[1] = a->g_translation_p1;
-  const int pose_bwd = (a->g_axisangle_m1 || a->g_translation_m1 || a->g_axisangle_p1 || a->g_translation_p1) ? 1 : 0;
+  StepAssemble as = {};
+  as.G_r_t = w.G_r_t; as.G_r_s = w.G_r_s; as.G_cd = w.G_c; as.gn_t = w.gn_t; as.gn_s = w.gn_s;
+  as.coefs = w.coefs; as.stats = w.sm_stats; as.g_total = a->g_total; as.B = B; as.HW = HW; as.W = W;
+  as.gT0 = w.gT[0]; as.gT1 = w.gT[1]; as.gTs0 = w.gTs[0]; as.gTs1 = w.gTs[1];
+  as.g_disp_t = teacher_done ? nullptr : a->g_disp_teacher; as.g_disp_s = a->g_disp_student;
+  as.pose_bwd = (a->g_axisangle_m1 || a->g_translation_m1 || a->g_axisangle_p1 || a->g_translation_p1) ? 1 : 0;
+  as.bgP = per_sample_t ? w.bgP : nullptr; as.K = a->K; as.per_sample = per_sample_t;
+  as.bnd_t = g_march_halo1 ? w.bnd_t : nullptr; as.bnd_s = g_march_halo1 ? w.bnd_s : nullptr; as.rows = rows; as.segs = segs;
+  as.fix_t = teacher_done ? a->g_disp_teacher : nullptr;
+  as.G_e = a->ens_disp ? w.G_e : nullptr; as.g_ens = a->ens_disp ? a->g_ens_disp : nullptr;
+  as.G_dual = (a->flags & MAL_STEP_DUAL_DISTIL) ? w.G_e : nullptr;
   auto assemble = [&](int parts, hipStream_t on) {
-    hipLaunchKernelGGL(step_assemble_kernel, dim3((unsigned)g), dim3(256), 0, on, w.G_r_t, w.G_r_s, w.G_c, w.gn_t,
-                       w.gn_s, w.coefs, w.sm_stats, a->g_total, B, HW, w.gT[0], w.gT[1], w.gTs[0], w.gTs[1],
-                       teacher_done ? nullptr : a->g_disp_teacher, a->g_disp_student, pp, pose_bwd, per_sample_t ? w.bgP : nullptr,
-                       a->K, per_sample_t, W, g_march_halo1 ? w.bnd_t : nullptr, g_march_halo1 ? w.bnd_s : nullptr, rows, segs,
-                       teacher_done ? a->g_disp_teacher : nullptr, a->ens_disp ? w.G_e : nullptr,
-                       a->ens_disp ? a->g_ens_disp : nullptr, (a->flags & MAL_STEP_DUAL_DISTIL) ? w.G_e : nullptr, parts);
+    as.parts = parts;
+    hipLaunchKernelGGL(step_assemble_kernel, dim3((unsigned)g), dim3(256), 0, on, as, pp);
     return launch_status();
   };
   if (tail) {

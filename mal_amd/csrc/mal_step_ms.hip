@@ -16,26 +16,9 @@
 #include "mal_march.h"
 #include "mal_device.h"
 #include "mal_pose.h"
+#include "mal_tail.h"
 
 namespace mal {
-extern opt_t g_march_halo1;  // mal_step.hip
-
-// mal_photo_march.hip / mal_step.hip
-int smooth_march_sweep_batch(int n, const float* const* disp, const float* const* img, int B, const int* H, const int* W,
-                             float* const* gn, double* const* partial, hipStream_t st, int* per_sample);
-int photo_march_fused_more(const float* target, const float* cand0, const float* cand1, int idx0, const float* ident,
-                           const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H, int W,
-                           float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
-                           float* g_cand1, int* per_sample_out, hipStream_t st, const uint8_t* region, float* g_region0,
-                           float* g_region1, unsigned* order, unsigned* order_count, const float* orig0, const float* orig1,
-                           size_t orig_stride, int target_texels, int weight_given);
-int smooth_march_batch_tasks(int H, int W);
-// mal_step.hip: the library's side stream of the caller's stream (fork / join through events: capturable)
-hipStream_t side_begin(hipStream_t st);
-int side_end(hipStream_t st);
-int side_wait(hipStream_t st, bool always);
-int tiebreak_noise_launch(unsigned long long seed, unsigned long long step, const unsigned long long* counter, unsigned mult,
-                          int n, int B, int H, int W, float* const* out, hipStream_t st);
 
 constexpr int kMsS = MAL_MS_MAX_SCALES;
 // option "ms_fold" (A/B): 0 = the noise maps and the upsampling as launches of their own behind the first sweep.  Worth 0.6 %
@@ -201,27 +184,8 @@ struct MsFinal {
 MAL_DEV void ms_pose_block(const float* bgP, int per_sample, const float* K, float* gT, int s, int b, int B, double* s_part,
                            double* s_gP) {
   const int tid = threadIdx.x;
-  const int v = tid % 24, sub = tid / 24;
-  double acc = 0.0;
-  if (sub < 10) {
-#pragma unroll 8
-    for (int t = sub; t < per_sample; t += 10) acc += (double)bgP[((size_t)b * per_sample + t) * 24 + v];
-  }
-  s_part[tid] = acc;
-  __syncthreads();
-  if (tid < 24) {
-    double a = 0.0;
-    for (int k = 0; k < 10; ++k) a += s_part[k * 24 + tid];
-    s_gP[tid] = a;
-  }
-  __syncthreads();
-  if (tid < 32) {
-    const int f = tid >> 4, e = tid & 15, k = e >> 2, j = e & 3;
-    const float* Kb = K + b * 16;
-    double a = 0.0;
-    for (int i = 0; i < 3; ++i) a += (double)Kb[i * 4 + k] * s_gP[f * 12 + i * 4 + j];
-    gT[((size_t)(s * 2 + f) * B + b) * 16 + e] = (float)a;
-  }
+  const double a = tail_pose_block(bgP, per_sample, K, b, s_part, s_gP);
+  if (tid < 32) gT[((size_t)(s * 2 + (tid >> 4)) * B + b) * 16 + (tid & 15)] = (float)a;
 }
 struct MsPose { const float* bgP[kMsS]; const float* K; float* gT; int per_sample, B; };
 // temporal hint: the teacher's gradient sweeps run in the backward call; S*B workgroups reduce their pose partials there
@@ -239,7 +203,6 @@ __global__ __launch_bounds__(256) void ms_final_kernel(MsFinal p) {
   __shared__ double s_part[256];
   __shared__ double s_gP[24];
   __shared__ double sh_tot[2 * kMsS][8];
-  __shared__ unsigned s_last;
   const int tid = threadIdx.x, B = p.B, S = p.S;
   if ((int)blockIdx.x < 2 * S * B) {
     const int pass = blockIdx.x / B, b = blockIdx.x - pass * B, net = pass / S, s = pass - net * S;
@@ -249,71 +212,16 @@ __global__ __launch_bounds__(256) void ms_final_kernel(MsFinal p) {
     const size_t stride = j < 4 ? 8 : 4;
     const double* q = j < 4 ? p.bs[net][s] + (size_t)b * ps_n * 8 + j
                             : p.sm[net][s] + (size_t)b * p.per_sample_sm[s] * 4 + (j - 4);
-    double acc = 0.0;
-#pragma unroll 8
-    for (int t = sub; t < n_t; t += 32) acc += q[(size_t)t * stride];
-    if (net == 0 && p.bs_ph[s] && j < 2) {
-      const double* bd = p.bs_ph[s] + (size_t)b * p.per_sample_ph[s] * 2 + j;
-#pragma unroll 8
-      for (int t = sub; t < p.per_sample_ph[s]; t += 32) acc += bd[(size_t)t * 2];
-    }
-    s_part[tid] = acc;
-    __syncthreads();
-    if (tid < 8) {
-      double a = 0.0;
-      for (int k = 0; k < 32; ++k) a += s_part[k * 8 + tid];
-      p.ps[((size_t)pass * B + b) * 8 + tid] = a;
-    }
+    double acc = tail_strided_sum(0.0, q, stride, n_t, sub);
+    if (net == 0 && p.bs_ph[s] && j < 2) acc = tail_strided_sum(acc, p.bs_ph[s] + (size_t)b * p.per_sample_ph[s] * 2 + j, 2, p.per_sample_ph[s], sub);
+    tail_sample_sums(acc, s_part, p.ps + ((size_t)pass * B + b) * 8);
   } else {
     const int r = blockIdx.x - 2 * S * B, s = r / B, b = r - s * B;
     ms_pose_block(p.bgP[s], p.per_sample, p.K, p.gT, s, b, B, s_part, s_gP);
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(p.ticket, 1u);
-  __syncthreads();
-  if (s_last != gridDim.x - 1) return;
-  __threadfence();
-  // per-sample statistics of the smoothness gradient (mean of the scale's own disparity map)
-  for (int i = tid; i < 2 * S * B; i += 256) {
-    const int s = (i / B) % S;
-    const double hw = (double)((p.H >> s) * (p.W >> s));
-    const double* q = p.ps + (size_t)i * 8;
-    const double mean = q[7] / hw;
-    const double m = (double)((float)mean + 1e-7f);
-    p.stats[i] = mean;
-    p.stats[2 * S * B + i] = q[6] / (hw * m * m);
-  }
-  // sums over samples in sample order; the smoothness slots weighted by the sample's 1/(mean + 1e-7).  One thread per
-  // (pass, sample, slot) fetches and weighs its term (one round trip for all), 8 threads per pass then add B terms.
-  constexpr int kStage = 2 * kMsS * 16 * 8;  // staged in LDS up to B = 16; beyond, the summing threads re-fetch
-  __shared__ double s_term[kStage];
-  const bool staged = 2 * S * B * 8 <= kStage;
-  for (int i = tid; staged && i < 2 * S * B * 8; i += 256) {
-    const int j = i & 7, s = ((i >> 3) / B) % S;
-    const double* q = p.ps + (size_t)(i >> 3) * 8;
-    double v = q[j];
-    if (j == 4 || j == 5) v = v * (double)div_(1.0f, (float)(q[7] / (double)((p.H >> s) * (p.W >> s))) + 1e-7f);
-    s_term[i] = v;
-  }
-  __syncthreads();
-  if (tid < 2 * S * 8) {
-    const int pass = tid >> 3, j = tid & 7, s = pass % S;
-    const double hw = (double)((p.H >> s) * (p.W >> s));
-    double a = 0.0;
-    for (int b = 0; b < B; ++b) {
-      double v;
-      if (staged) v = s_term[((size_t)pass * B + b) * 8 + j];
-      else {
-        const double* q = p.ps + ((size_t)pass * B + b) * 8;
-        v = q[j];
-        if (j == 4 || j == 5) v = v * (double)div_(1.0f, (float)(q[7] / hw) + 1e-7f);
-      }
-      a += v;
-    }
-    sh_tot[pass][j] = a;
-  }
-  __syncthreads();
+  if (!tail_last_workgroup(p.ticket)) return;
+  // per-sample statistics of the smoothness gradient (mean of the scale's own disparity map) and the sums over samples
+  tail_sum_over_samples(p.ps, 2 * S, S, B, p.H, p.W, p.stats, sh_tot);
   // one thread per (network, scale): its four scalars and its coefficient (double divisions: not on one thread in a row)
   __shared__ float s_loss[2 * kMsS], s_rep[2 * kMsS], s_ens[2 * kMsS];
   if (tid < 2 * S) {
@@ -359,12 +267,7 @@ __global__ __launch_bounds__(256) void ms_final_kernel(MsFinal p) {
 // last row); the scratch row is added to the pass's gradient map in place (one add per element, fixed order).
 struct MsFold { float* G[2 * kMsS]; const float* bnd[2 * kMsS]; int B, H, W, rows, segs; };
 __global__ __launch_bounds__(256) void ms_fold_kernel(MsFold p) {
-  const int which = blockIdx.x & 1, bs = blockIdx.x >> 1, seg = bs % p.segs, b = bs / p.segs;
-  if ((which == 0 && seg == 0) || (which == 1 && seg == p.segs - 1)) return;  // the image's own border: nobody beyond it
-  const int y = which == 0 ? seg * p.rows : min(seg * p.rows + p.rows, p.H) - 1;
-  float* g = p.G[blockIdx.y] + ((size_t)b * p.H + y) * p.W;
-  const float* r = p.bnd[blockIdx.y] + ((size_t)(b * p.segs + seg) * 2 + which) * p.W;
-  for (int x = threadIdx.x; x < p.W; x += 256) g[x] += r[x];
+  tail_fold_boundary_row(p.G[blockIdx.y], p.bnd[blockIdx.y], (int)blockIdx.x, p.H, p.W, p.rows, p.segs);
 }
 
 
@@ -419,7 +322,7 @@ __global__ __launch_bounds__(256) void ms_assemble_kernel(MsAssemble p, PosePara
       const unsigned q = t * 4u;
       if (q >= npix) return;
       const unsigned b = q / hw;
-      const float inv = div_(1.0f, (float)p.stats[pass * B + b] + 1e-7f), corr = (float)p.stats[2 * S * B + pass * B + b];
+      const float inv = tail_inv_mean(p.stats[pass * B + b]), corr = (float)p.stats[2 * S * B + pass * B + b];
       const float4 r = *reinterpret_cast<const float4*>(G_r + q), n4 = *reinterpret_cast<const float4*>(gn + q);
       float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
       if (G_c) c = *reinterpret_cast<const float4*>(G_c + q);
@@ -429,16 +332,16 @@ __global__ __launch_bounds__(256) void ms_assemble_kernel(MsAssemble p, PosePara
       for (int e = 0; e < 4; ++e) {
         float v = cR * rr[e];
         if (G_c) v = fma_(g, cc[e], v);
-        o[e] = v + cS * (nn[e] * inv - corr);
+        o[e] = v + tail_smooth_grad(cS, nn[e], inv, corr);
       }
       *reinterpret_cast<float4*>(out + q) = make_float4(o[0], o[1], o[2], o[3]);
     } else {
       if (t >= npix) return;
       const unsigned b = t / hw;
-      const float inv = div_(1.0f, (float)p.stats[pass * B + b] + 1e-7f), corr = (float)p.stats[2 * S * B + pass * B + b];
+      const float inv = tail_inv_mean(p.stats[pass * B + b]), corr = (float)p.stats[2 * S * B + pass * B + b];
       float v = cR * G_r[t];
       if (G_c) v = fma_(g, G_c[t], v);
-      out[t] = v + cS * (gn[t] * inv - corr);
+      out[t] = v + tail_smooth_grad(cS, gn[t], inv, corr);
     }
     return;
   }
@@ -450,9 +353,9 @@ __global__ __launch_bounds__(256) void ms_assemble_kernel(MsAssemble p, PosePara
   const int i = (int)(pix / (unsigned)w), j = (int)(pix - (unsigned)i * (unsigned)w);
   const size_t ob = (size_t)b * H * W;
   const float gnv = gn[qq];
-  const float inv = div_(1.0f, (float)p.stats[pass * B + b] + 1e-7f), corr = (float)p.stats[2 * S * B + pass * B + b];
+  const float inv = tail_inv_mean(p.stats[pass * B + b]), corr = (float)p.stats[2 * S * B + pass * B + b];
   const float v = adjoint_gather(p.G_r[net][s] + ob, cR, G_c ? G_c + ob : nullptr, g, i, j, k, f, h, w, H, W);
-  if (live && k == 0) out[q] = v + cS * (gnv * inv - corr);
+  if (live && k == 0) out[q] = v + tail_smooth_grad(cS, gnv, inv, corr);
 }
 
 }  // namespace mal

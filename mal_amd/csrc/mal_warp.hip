@@ -14,6 +14,7 @@
 // per workgroup -> fixed-order second stage (bitwise reproducible, no atomics).
 #include "mal_common.h"
 #include "mal_device.h"
+#include "mal_tail.h"
 
 namespace mal {
 
@@ -163,30 +164,12 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(WarpParams p) {
 __global__ __launch_bounds__(256) void pose_grad_finalize_kernel(const float* block_gP, const float* K, int bps, int F,
                                                                  float* gT0, float* gT1) {
   __shared__ double s_gP[24];
-  __shared__ double s_part[240];
+  __shared__ double s_part[256];
   const int b = blockIdx.x, tid = threadIdx.x;
-  // 24 sums of bps partials: 10 threads per value (independent loads issued together), then a 10-term sum, fixed order
-  if (tid < 240) {
-    const int v = tid % 24, sub = tid / 24;
-    double acc = 0.0;
-#pragma unroll 4
-    for (int t = sub; t < bps; t += 10) acc += (double)block_gP[((size_t)b * bps + t) * 24 + v];
-    s_part[tid] = acc;
-  }
-  __syncthreads();
-  if (tid < 24) {
-    double acc = 0.0;
-    for (int k = 0; k < 10; ++k) acc += s_part[k * 24 + tid];
-    s_gP[tid] = acc;
-  }
-  __syncthreads();
+  const double a = tail_pose_block(block_gP, bps, K, b, s_part, s_gP);  // the one-call steps' reduction: same order, same bits
   if (tid < 16 * F) {
-    int f = tid >> 4, e = tid & 15, k = e >> 2, j = e & 3;
-    const float* Kb = K + b * 16;
-    double acc = 0.0;
-    for (int i = 0; i < 3; ++i) acc += (double)Kb[i * 4 + k] * s_gP[f * 12 + i * 4 + j];
-    float* out = f ? gT1 : gT0;
-    if (out) out[b * 16 + e] = (float)acc;
+    float* out = (tid >> 4) ? gT1 : gT0;
+    if (out) out[b * 16 + (tid & 15)] = (float)a;
   }
 }
 
