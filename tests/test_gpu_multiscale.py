@@ -254,9 +254,12 @@ def check_multiscale_decision_exact(batch, kw, nt, matching, synth_of=None, retu
 
 @pytest.mark.parametrize("case", [(12, 192, 640, 3, True, False), (3, 40, 72, 2, False, False), (2, 32, 64, 0, True, False),
                                   (12, 192, 640, 3, True, True), (3, 40, 72, 2, False, True),
-                                  (17, 16, 32, 3, True, False)],  # S*B = 68 > 64: the reduction re-fetches instead of staging in LDS
+                                  # mal_tail.h stages passes * B * 8 terms in LDS up to kTailStage = 1024 (8 passes at sclm = 3): 1024 at
+                                  # B = 16, the last staged size; 1088 at B = 17, where the summing threads re-fetch theirs
+                                  (16, 16, 32, 3, True, False), (17, 16, 32, 3, True, False)],
                          ids=["baseline-b12-192x640-sclm3", "b3-40x72-sclm2", "b2-32x64-sclm0",
-                              "baseline-b12-192x640-sclm3-temporal", "b3-40x72-sclm2-temporal", "b17-16x32-sclm3-refetch"])
+                              "baseline-b12-192x640-sclm3-temporal", "b3-40x72-sclm2-temporal", "b16-16x32-sclm3-last-staged",
+                              "b17-16x32-sclm3-refetch"])
 def test_against_the_oracle(case):
     """decision-exact (round 5; rounds 2-4 held the pose gradients of this route at 2e-2 and exempted up to 2 % of the pixels)"""
     from mal_amd.synthetic import fake_image_synthesis
