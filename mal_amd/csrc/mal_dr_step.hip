@@ -47,7 +47,7 @@ static DrWs carve_dr(void* base, int B, int H, int W, int n) {
   char* p = (char*)base;
   size_t o = 0;
   const size_t HW = (size_t)H * W, map = B * HW * sizeof(float), nb = ws_blocks(B, H, W);
-  auto take = [&](size_t bytes) { char* r = p + o; o += align256(bytes); return r; };
+  auto take = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align256(bytes); return r; };  // (null base: sizing only)
   for (int i = 0; i < 3; ++i) w.packed[i] = (float*)take(B * HW * kTexel * sizeof(float));
   w.ident = (float*)take(map);
   for (int it = 0; it < n; ++it) {
@@ -303,6 +303,21 @@ extern "C" size_t mal_dr_workspace_bytes(int B, int H, int W, int n_iters) {
   return carve_dr(nullptr, B, H, W, n_iters).bytes;
 }
 
+// what the prologue works on, per slot (iteration, then the pose-update pass), for both of its forms: X = DrExtra (riding on the
+// identity / packing sweep) or DrPrologue (a launch of its own); group = pixel groups per noise workgroup
+template <class X>
+static void dr_prologue_fill(X& x, const mal_dr_args* a, const DrWs& w, int pu, bool philox, int group) {
+  const int B = a->B, H = a->H, W = a->W, n = a->n_iters;
+  x.K = a->K; x.invK = a->inv_K; x.seed = a->noise_seed; x.step = a->noise_step;
+  x.counter = (const unsigned long long*)a->noise_counter;
+  x.B = B; x.H = H; x.W = W; x.ticket = w.ticket; x.pu_slot = pu ? n : -1;
+  x.noise_blocks = philox ? (int)(((size_t)B * ((H + 3) / 4) * W + group - 1) / group) : 0;
+  for (int it = 0; it < n + pu; ++it) {
+    x.T[it][0] = it < n ? a->T_m1[it] : a->pu_T_m1; x.T[it][1] = it < n ? a->T_p1[it] : a->pu_T_p1;
+    x.cam[it] = w.cam[it]; x.noise[it] = w.noise[it];
+  }
+}
+
 extern "C" int mal_dr_loss_fwd(const mal_dr_args* a) {
   int rc = dr_check(a);
   if (rc) return rc;
@@ -325,46 +340,35 @@ extern "C" int mal_dr_loss_fwd(const mal_dr_args* a) {
     const DrWs w0 = carve_dr(const_cast<void*>(a->texels_from), B, H, W, 1);
     for (int i = 0; i < 3; ++i) w.packed[i] = w0.packed[i];
     w.ident = w0.ident;
+    DrPrologue q = {};  // (no sweep in this call: the prologue is a launch of its own)
+    dr_prologue_fill(q, a, w, pu, philox, 256);
+    hipLaunchKernelGGL(dr_prologue_kernel, dim3((unsigned)(q.noise_blocks + B), (unsigned)(n + pu)), dim3(256), 0, st, q);
+    rc = launch_status();
   } else {
     SmoothParams sm = {};
     sm.n = n; sm.partials = w.sm[0];
     for (int it = 0; it < n && smooth_fused; ++it) { sm.disp[it] = a->disp[it]; sm.gn[it] = w.gn[it]; }
     // ... and the prologue (camera blocks, noise maps: nothing the sweep reads or writes) as the same launch's last workgroups
     DrExtra x = {};
-    x.K = a->K; x.invK = a->inv_K; x.seed = a->noise_seed; x.step = a->noise_step;
-    x.counter = (const unsigned long long*)a->noise_counter;
-    x.B = B; x.H = H; x.W = W; x.ticket = w.ticket; x.slots = n + pu; x.pu_slot = pu ? n : -1;
-    x.noise_blocks = philox ? (int)(((size_t)B * ((H + 3) / 4) * W + 63) / 64) : 0;
-    for (int it = 0; it < n; ++it) { x.T[it][0] = a->T_m1[it]; x.T[it][1] = a->T_p1[it]; x.cam[it] = w.cam[it]; x.noise[it] = w.noise[it]; }
-    if (pu) { x.T[n][0] = a->pu_T_m1; x.T[n][1] = a->pu_T_p1; x.cam[n] = w.cam[n]; x.noise[n] = w.noise[n]; }
-    rc = pack_identity_launch(a->color0, a->color_m1, a->color_p1, B, H, W, w.packed[1], w.packed[2], w.packed[0], w.ident, st,
-                              nullptr, nullptr, smooth_fused ? &sm : nullptr, &per_sample_sm, false, variant, &x);
-    if (rc) return rc;
+    dr_prologue_fill(x, a, w, pu, philox, 64);
+    x.slots = n + pu;
+    PackIdentityArgs pk = {};
+    pk.target = a->color0; pk.src[0] = a->color_m1; pk.src[1] = a->color_p1;
+    pk.packed[0] = w.packed[1]; pk.packed[1] = w.packed[2]; pk.packed_target = w.packed[0]; pk.ident = w.ident;
+    pk.smooth = smooth_fused ? &sm : nullptr; pk.variant = variant; pk.dr = &x;
+    rc = pack_identity_launch(pk, B, H, W, st, &per_sample_sm);
   }
-  if (reuse) {  // (no sweep in this call: the prologue is a launch of its own)
-    DrPrologue q = {};
-    q.K = a->K; q.invK = a->inv_K; q.seed = a->noise_seed; q.step = a->noise_step;
-    q.counter = (const unsigned long long*)a->noise_counter;
-    q.B = B; q.H = H; q.W = W; q.ticket = w.ticket;
-    q.noise_blocks = philox ? (int)(((size_t)B * ((H + 3) / 4) * W + 255) / 256) : 0;
-    for (int it = 0; it < n; ++it) { q.T[it][0] = a->T_m1[it]; q.T[it][1] = a->T_p1[it]; q.cam[it] = w.cam[it]; q.noise[it] = w.noise[it]; }
-    q.pu_slot = pu ? n : -1;
-    if (pu) { q.T[n][0] = a->pu_T_m1; q.T[n][1] = a->pu_T_p1; q.cam[n] = w.cam[n]; q.noise[n] = w.noise[n]; }
-    hipLaunchKernelGGL(dr_prologue_kernel, dim3((unsigned)(q.noise_blocks + B), (unsigned)(n + pu)), dim3(256), 0, st, q);
-    rc = launch_status();
-    if (rc) return rc;
-  }
+  if (rc) return rc;
   const int packed = MAL_F_SRC_PACKED | MAL_F_TGT_PACKED;
   const float merge_cons = (float)(1.0 / ((double)B * H * W));
   int per_sample = 1;
   for (int it = 0; it < n; ++it) {
-    MarchParams p = march_params(B, H, W, a->min_depth, a->max_depth, 1e-7f, 1);  // convention B
-    p.disp = a->disp[it]; p.K = a->K; p.invK = a->inv_K; p.T[0] = a->T_m1[it]; p.T[1] = a->T_p1[it];
-    p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+    // convention B; the poses differ per iteration: its own camera block (dr_prologue_kernel)
+    MarchParams p = step_march_params(a, 1, a->T_m1[it], a->T_p1[it], w.packed, w.cam[it]);
+    p.disp = a->disp[it];
     p.ident = w.ident; p.noise = automask ? (philox ? w.noise[it] : a->noise[it]) : nullptr;
     p.g_reproj = w.G_r[it]; p.block_sums = w.bs[it]; p.block_gP = w.bgP[it];
-    p.bnd = g_march_halo1 ? w.bnd[it] : nullptr;
-    p.cam = w.cam[it]; p.cam_ready = 1;  // the poses differ per iteration: its own camera block (dr_prologue_kernel)
+    p.bnd = halo_bnd(w.bnd[it]);
     p.avg = (a->flags & MAL_DR_AVG) ? 1 : 0; p.no_ssim = (a->flags & MAL_DR_NO_SSIM) ? 1 : 0;
     int flags = MAL_F_GRAD | MAL_F_POSE_GRAD | (automask ? MAL_F_AUTOMASK : 0) | packed;
     if (it > 0) {  // x consistency_mask, consistency term against iteration 0's depth (its disparity, no gradient to it)
@@ -381,14 +385,11 @@ extern "C" int mal_dr_loss_fwd(const mal_dr_args* a) {
   if (pu) {
     // the pose-update losses (dualrefine/trainer.py:457-480,699-767): min over {frame -1 under the refined pose with the last
     // iteration's disparity, frame +1 as iteration 0 warped it}, automask with a noise draw of its own, no mask, no epilogue
-    MarchParams p = march_params(B, H, W, a->min_depth, a->max_depth, 1e-7f, 1);
+    MarchParams p = step_march_params(a, 1, a->pu_T_m1, a->pu_T_p1, w.packed, w.cam[n]);
     p.disp = a->pu_disp_m1; p.disp2 = a->pu_disp_p1; p.framed = 1;
-    p.K = a->K; p.invK = a->inv_K; p.T[0] = a->pu_T_m1; p.T[1] = a->pu_T_p1;
-    p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
     p.ident = w.ident; p.noise = automask ? (philox ? w.noise[n] : a->pu_noise) : nullptr;
     p.g_reproj = w.G_r[n]; p.g_reproj2 = w.G_r2; p.block_sums = w.bs[n]; p.block_gP = w.bgP[n];
-    p.bnd = g_march_halo1 ? w.bnd[n] : nullptr; p.bnd2 = g_march_halo1 ? w.bnd2 : nullptr;
-    p.cam = w.cam[n]; p.cam_ready = 1;
+    p.bnd = halo_bnd(w.bnd[n]); p.bnd2 = halo_bnd(w.bnd2);
     p.avg = (a->flags & MAL_DR_AVG) ? 1 : 0; p.no_ssim = (a->flags & MAL_DR_NO_SSIM) ? 1 : 0;
     p.dbg = a->pu_dec;
     rc = march_launch(p, MAL_F_GRAD | MAL_F_POSE_GRAD | (automask ? MAL_F_AUTOMASK : 0) | packed, st);
@@ -397,15 +398,11 @@ extern "C" int mal_dr_loss_fwd(const mal_dr_args* a) {
   }
   DrFinal fin = {};
   if (!smooth_fused) {
-    const float *sd[kDrIt], *si[kDrIt];
-    float* sg[kDrIt];
-    double* sp[kDrIt];
-    int sh[kDrIt], sw[kDrIt], per[kDrIt];
-    for (int it = 0; it < n; ++it) {
-      sd[it] = a->scale ? a->disp_lo[it] : a->disp[it]; si[it] = a->scale ? a->color0_s : a->color0;
-      sg[it] = w.gn[it]; sp[it] = w.sm[it]; sh[it] = hs; sw[it] = wsz;
-    }
-    rc = smooth_march_sweep_batch(n, sd, si, B, sh, sw, sg, sp, st, per);
+    SmoothMapArgs maps[kDrIt];
+    int per[kDrIt];
+    for (int it = 0; it < n; ++it)
+      maps[it] = {a->scale ? a->disp_lo[it] : a->disp[it], a->scale ? a->color0_s : a->color0, hs, wsz, w.gn[it], w.sm[it]};
+    rc = smooth_march_sweep_batch(n, maps, B, st, per);
     if (rc) return rc;
     fin.per_sample_sm = per[0]; fin.sm_stride = 4;
     for (int it = 0; it < n; ++it) fin.sm[it] = w.sm[it];
@@ -433,13 +430,13 @@ extern "C" int mal_dr_loss_bwd(const mal_dr_args* a) {
   if (rc) return rc;
   DrAssemble p = {};
   for (int it = 0; it < n; ++it) {
-    p.G_r[it] = w.G_r[it]; p.G_c[it] = w.G_c[it]; p.gn[it] = w.gn[it]; p.bnd[it] = g_march_halo1 ? w.bnd[it] : nullptr;
+    p.G_r[it] = w.G_r[it]; p.G_c[it] = w.G_c[it]; p.gn[it] = w.gn[it]; p.bnd[it] = halo_bnd(w.bnd[it]);
     p.g_disp[it] = a->g_disp[it]; p.g_T[it][0] = a->g_T_m1[it]; p.g_T[it][1] = a->g_T_p1[it];
     p.g_disp_lo[it] = a->scale ? a->g_disp_lo[it] : nullptr;
   }
   const int pu = (a->flags & MAL_DR_POSE_UPDATE) ? 1 : 0;
   if (pu) {
-    p.G_r[n] = w.G_r[n]; p.G_r2 = w.G_r2; p.bnd[n] = g_march_halo1 ? w.bnd[n] : nullptr; p.bnd2 = g_march_halo1 ? w.bnd2 : nullptr;
+    p.G_r[n] = w.G_r[n]; p.G_r2 = w.G_r2; p.bnd[n] = halo_bnd(w.bnd[n]); p.bnd2 = halo_bnd(w.bnd2);
     p.g_disp[n] = a->g_pu_disp_m1; p.g_disp2 = a->g_pu_disp_p1; p.g_T[n][0] = a->g_pu_T_m1; p.g_T[n][1] = a->g_pu_T_p1;
     p.g_pu_total = a->g_pu_total;
     p.pu_on = 1;

@@ -114,6 +114,11 @@ bool march_pair_qualifies(int B, int H, int W);
 int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStream_t st);
 // the decomposition march_launch picks for (B,H,W) and `flags` on the current device
 void march_geometry(int B, int H, int W, int flags, int* strips, int* segs, int* rows);
+inline int march_tasks_per_sample(int B, int H, int W, int flags) {
+  int strips = 0, segs = 0;
+  march_geometry(B, H, W, flags, &strips, &segs, nullptr);
+  return strips * segs;
+}
 // the one-call steps: the first call of a step records the decomposition it uses for workspace `ws`; the later calls check
 // that the options still give the same one (MAL_ESTALE otherwise)
 void step_geom_record(const void* ws, int B, int H, int W);
@@ -165,25 +170,23 @@ struct DrExtra {
   unsigned long long seed, step; const unsigned long long* counter;
   int slots, pu_slot, noise_blocks, B, H, W; unsigned* ticket;
 };
-// the arguments of one fused sweep over a materialised candidate pair (photo_march_fused_more, mal_photo_march.hip), for the
-// batched launch photo_march_fused_more_n
+// One fused sweep over a materialised candidate pair (mal_photo_march.hip): candidates (cand0, cand1) = indices (idx0, idx0+1)
+// join the running min prev_min / prev_arg; weight_given: `ident` holds the pass's weight instead of the identity term.
+// The one description of a sweep: the single launch (photo_march_fused_more; order / order_count: the task order of a
+// region-gated sweep, experiments build) and the batched one (photo_march_fused_more_n, n sweeps of one shape) both take it.
 struct FusedMoreArgs {
   const float* target; const float* cand0; const float* cand1; int idx0; const float* ident; const float* noise;
   const float* prev_min; const uint8_t* prev_arg; float* min_reproj; uint8_t* argmin; float* weight_out; double* block_sums;
   float* g_cand0; float* g_cand1; const uint8_t* region; float* g_region0; float* g_region1; const float* orig0; const float* orig1;
   size_t orig_stride; int weight_given;
 };
+int photo_march_fused_more(const FusedMoreArgs& a, int B, int H, int W, int* per_sample_out, hipStream_t st,
+                           unsigned* order = nullptr, unsigned* order_count = nullptr);
 int photo_march_fused_more_n(int n, const FusedMoreArgs* a, int B, int H, int W, int* per_sample_out, hipStream_t st);
-// mal_photo_march.hip: one such sweep (the arguments are FusedMoreArgs' + the task order of a region-gated sweep); the batched
-// edge-aware smoothness sweep over n <= 8 maps (per_sample[k]: tasks per sample of map k) and its tasks per sample of one map
-int photo_march_fused_more(const float* target, const float* cand0, const float* cand1, int idx0, const float* ident,
-                           const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H, int W,
-                           float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
-                           float* g_cand1, int* per_sample_out, hipStream_t st, const uint8_t* region, float* g_region0,
-                           float* g_region1, unsigned* order, unsigned* order_count, const float* orig0, const float* orig1,
-                           size_t orig_stride, int target_texels, int weight_given);
-int smooth_march_sweep_batch(int n, const float* const* disp, const float* const* img, int B, const int* H, const int* W,
-                             float* const* gn, double* const* partial, hipStream_t st, int* per_sample);
+// the batched edge-aware smoothness sweep over n <= 8 maps, each at its own size (per_sample[k]: tasks per sample of map k),
+// and its tasks per sample of one map
+struct SmoothMapArgs { const float* disp; const float* img; int H, W; float* gn; double* partial; };
+int smooth_march_sweep_batch(int n, const SmoothMapArgs* maps, int B, hipStream_t st, int* per_sample);
 int smooth_march_batch_tasks(int H, int W);
 // mal_step.hip: the library's side stream of the caller's stream (fork / join through events: capturable) and the launch of
 // n <= 4 tie-break noise maps
@@ -201,12 +204,56 @@ struct MsExtra {
   UpMaps up; int n_up;            // maps to upsample, four output pixels per thread (W % 4 == 0, 16-byte aligned destinations)
   int B, H, W, noise_blocks, up_blocks;  // 64-thread workgroups per noise map / per upsampled map
 };
-int pack_identity_launch(const float* target, const float* src0, const float* src1, int B, int H, int W,
-                         float* packed0, float* packed1, float* packed_target, float* ident, hipStream_t st,
-                         const StepPoses* poses = nullptr, const TieNoise* noise = nullptr,
-                         const SmoothParams* smooth = nullptr, int* tasks_per_sample = nullptr, bool texel_in = false,
-                         int variant = 0 /* bit 0 --no_ssim, bit 1 --avg_reprojection: the identity term follows */,
-                         const DrExtra* dr = nullptr, const MsExtra* ms = nullptr);
+// the operands of the identity / packing sweep: the three images (planar, or -- texel_in -- the texels themselves: nothing is
+// repacked, packed* null), the texel outputs (packed[f] of src[f], nullable together; packed_target nullable), the identity
+// map, and what rides on the launch (all nullable); variant: bit 0 --no_ssim, bit 1 --avg_reprojection (the identity term follows)
+struct PackIdentityArgs {
+  const float* target; const float* src[2]; float* packed[2]; float* packed_target; float* ident;
+  const StepPoses* poses; const TieNoise* noise; const SmoothParams* smooth; const DrExtra* dr; const MsExtra* ms;
+  bool texel_in; int variant;
+};
+int pack_identity_launch(const PackIdentityArgs& a, int B, int H, int W, hipStream_t st, int* tasks_per_sample = nullptr);
+
+// ---- builders of the one-call steps' launch records (mal_step.hip, mal_step_ms.hip, mal_dr_step.hip).  A = mal_step_args /
+// mal_ms_args / mal_dr_args: the fields they read carry the same names in all of them.
+// the block every marching pass of a step shares: shape, depth range, convention, intrinsics, the two poses, the step's texels
+// (packed[0] target, [1] frame -1, [2] frame +1) and the camera block its first sweep filled
+template <class A>
+MarchParams step_march_params(const A* a, int convention, const float* T0, const float* T1, float* const* packed, float* cam) {
+  MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, convention);
+  p.K = a->K; p.invK = a->inv_K; p.T[0] = T0; p.T[1] = T1;
+  p.src[0] = packed[1]; p.src[1] = packed[2]; p.target = packed[0];
+  p.cam = cam; p.cam_ready = 1;
+  return p;
+}
+// both frames' pose parameters (frame -1 is inverted, networks/repdepth.py:159-160)
+template <class A> PoseParams step_pose_inputs(const A* a) {
+  PoseParams pp = {};
+  pp.B = a->B; pp.F = 2;
+  pp.axisangle[0] = a->axisangle_m1; pp.axisangle[1] = a->axisangle_p1;
+  pp.translation[0] = a->translation_m1; pp.translation[1] = a->translation_p1;
+  pp.invert[0] = 1; pp.invert[1] = 0;
+  return pp;
+}
+// the pose workgroups of a step's first sweep: poses out to T, camera block, the last kernel's completion counter reset
+template <class A> StepPoses step_poses(const A* a, float* const* T, float* cam, unsigned* ticket) {
+  StepPoses sp = {};
+  sp.pose = step_pose_inputs(a);
+  sp.pose.T[0] = T[0]; sp.pose.T[1] = T[1];
+  sp.K = a->K; sp.invK = a->inv_K; sp.cam = cam; sp.ticket = ticket;
+  return sp;
+}
+// the pose backward of a step's assembly launch (gTs: the scaled pose gradients it reads); *pose_bwd: whether any is wanted
+template <class A> PoseParams step_pose_bwd(const A* a, float* const* gTs, int* pose_bwd) {
+  PoseParams pp = step_pose_inputs(a);
+  pp.gT[0] = gTs[0]; pp.gT[1] = gTs[1];
+  pp.g_axisangle[0] = a->g_axisangle_m1; pp.g_axisangle[1] = a->g_axisangle_p1;
+  pp.g_translation[0] = a->g_translation_m1; pp.g_translation[1] = a->g_translation_p1;
+  *pose_bwd = (a->g_axisangle_m1 || a->g_translation_m1 || a->g_axisangle_p1 || a->g_translation_p1) ? 1 : 0;
+  return pp;
+}
+// option "march_halo1": the boundary scratch rows of a gradient pass, or none (two-row halo)
+inline float* halo_bnd(float* bnd) { return g_march_halo1 ? bnd : nullptr; }
 
 // Philox4x32-10 (Salmon et al., SC'11; the generator behind torch's device randn), one block of four 32-bit words
 MAL_DEV void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {

@@ -1836,19 +1836,17 @@ int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStre
 
 int pack_identity_tasks_per_sample(int H, int W) { return ((W + 61) / 62) * ((H + g_pack_rows - 1) / g_pack_rows); }
 
-int pack_identity_launch(const float* target, const float* src0, const float* src1, int B, int H, int W,
-                         float* packed0, float* packed1, float* packed_target, float* ident, hipStream_t st,
-                         const StepPoses* poses, const TieNoise* noise, const SmoothParams* smooth, int* tasks_per_sample,
-                         bool texel_in, int variant, const DrExtra* dr, const MsExtra* ms) {
+int pack_identity_launch(const PackIdentityArgs& a, int B, int H, int W, hipStream_t st, int* tasks_per_sample) {
   IdentParams p = {};
-  p.variant = variant;
-  if (dr) { p.dr = *dr; p.dr_blocks = dr->slots * (dr->noise_blocks + dr->B); }
-  if (ms) { p.ms = *ms; p.ms_blocks = ms->n_noise * ms->noise_blocks + ms->n_up * ms->up_blocks; }
-  if (noise) p.tn = *noise;
-  if (smooth) p.sm = *smooth;
-  p.pose_blocks = poses ? B : 0;
-  if (poses) p.sp = *poses;
-  p.target = target; p.src[0] = src0; p.src[1] = src1; p.packed[0] = packed0; p.packed[1] = packed1; p.packed_target = packed_target; p.ident = ident;
+  p.variant = a.variant;
+  if (a.dr) { p.dr = *a.dr; p.dr_blocks = a.dr->slots * (a.dr->noise_blocks + a.dr->B); }
+  if (a.ms) { p.ms = *a.ms; p.ms_blocks = a.ms->n_noise * a.ms->noise_blocks + a.ms->n_up * a.ms->up_blocks; }
+  if (a.noise) p.tn = *a.noise;
+  if (a.smooth) p.sm = *a.smooth;
+  p.pose_blocks = a.poses ? B : 0;
+  if (a.poses) p.sp = *a.poses;
+  p.target = a.target; p.src[0] = a.src[0]; p.src[1] = a.src[1]; p.packed[0] = a.packed[0]; p.packed[1] = a.packed[1];
+  p.packed_target = a.packed_target; p.ident = a.ident;
   p.B = B; p.H = H; p.W = W;
   p.strips = (W + 61) / 62;
   p.rows = g_pack_rows;  // three waves per SIMD fit (launch bounds, <= 168 VGPRs with the smoothness terms)
@@ -1856,11 +1854,11 @@ int pack_identity_launch(const float* target, const float* src0, const float* sr
   p.ntasks = B * p.strips * p.segs;
   p.per_xcd = (p.ntasks + 7) / 8;
   if (tasks_per_sample) *tasks_per_sample = p.strips * p.segs;
-  if (variant) {  // --no_ssim / --avg_reprojection identity term: its own instantiation (the default one stays as it is)
-    if (texel_in) return MAL_EINVAL;
+  if (a.variant) {  // --no_ssim / --avg_reprojection identity term: its own instantiation (the default one stays as it is)
+    if (a.texel_in) return MAL_EINVAL;
     hipLaunchKernelGGL((pack_identity_kernel<false, true>), dim3(p.per_xcd * 8 + p.pose_blocks + p.dr_blocks + p.ms_blocks), dim3(64), 0, st, p);
-  } else if (texel_in) {
-    if (packed0 || packed1 || packed_target) return MAL_EINVAL;  // nothing to repack: the inputs are the texels
+  } else if (a.texel_in) {
+    if (a.packed[0] || a.packed[1] || a.packed_target) return MAL_EINVAL;  // nothing to repack: the inputs are the texels
     hipLaunchKernelGGL(pack_identity_kernel<true>, dim3(p.per_xcd * 8 + p.pose_blocks + p.dr_blocks + p.ms_blocks), dim3(64), 0, st, p);
   } else
   hipLaunchKernelGGL(pack_identity_kernel<false>, dim3(p.per_xcd * 8 + p.pose_blocks + p.dr_blocks + p.ms_blocks), dim3(64), 0, st, p);

@@ -645,20 +645,20 @@ int smooth_march_sweep(const float* disp, const float* img, int B, int H, int W,
 // tasks per sample of one (H, W) map in smooth_march_sweep_batch's decomposition
 int smooth_march_batch_tasks(int H, int W) { return ((W + 61) / 62) * ((H + 11) / 12); }
 // n <= 8 maps in one launch; per_sample[k] receives the tasks per sample of map k
-int smooth_march_sweep_batch(int n, const float* const* disp, const float* const* img, int B, const int* H, const int* W,
-                             float* const* gn, double* const* partial, hipStream_t st, int* per_sample) {
+int smooth_march_sweep_batch(int n, const SmoothMapArgs* maps, int B, hipStream_t st, int* per_sample) {
   if (n <= 0 || n > kSmoothBatch) return MAL_EINVAL;
   SmoothMarchBatch q = {};
   q.n = n;
   for (int k = 0; k < n; ++k) {
+    const SmoothMapArgs& m = maps[k];
     SmoothMarchParams& p = q.m[k];
-    p.disp = disp[k]; p.img = img[k]; p.gn = gn[k]; p.partial = partial[k]; p.B = B; p.H = H[k]; p.W = W[k];
-    p.strips = (W[k] + 61) / 62;
+    p.disp = m.disp; p.img = m.img; p.gn = m.gn; p.partial = m.partial; p.B = B; p.H = m.H; p.W = m.W;
+    p.strips = (m.W + 61) / 62;
     p.rows = 12;
-    p.segs = (H[k] + p.rows - 1) / p.rows;
+    p.segs = (m.H + p.rows - 1) / p.rows;
     p.ntasks = B * p.strips * p.segs;
     q.first[k + 1] = q.first[k] + p.ntasks;
-    if (per_sample) per_sample[k] = smooth_march_batch_tasks(H[k], W[k]);  // (= p.strips * p.segs)
+    if (per_sample) per_sample[k] = smooth_march_batch_tasks(m.H, m.W);  // (= p.strips * p.segs)
   }
   q.per_xcd = (q.first[n] + 7) / 8;
   hipLaunchKernelGGL(smooth_march_batch_kernel, dim3(q.per_xcd * 8), dim3(64), 0, st, q);
@@ -747,31 +747,43 @@ int photo_march_bwd(const float* target, const float* const* cand, int n_cand, c
   return launch_status();
 }
 
-// The temporal hint of the whole-step list in ONE sweep: candidates (cand0, cand1) = indices (idx0, idx0+1) join the
-// running min prev_min / prev_arg (read-only; must not alias the outputs), automask against ident (+ noise); the outputs
-// min_reproj / argmin / weight_out arrive holding the decision over the earlier candidates and are overwritten where this
-// pair is re-decided; per-task partials [task][2] = DIFFERENCES of sum(rp*w), sum(w) against that earlier decision; and
-// d sum(rp*w) / d candidate, unnormalised.  order (nullable): >= ntasks device words, order_count: two zeroed words.
-static int fused_more_params(PhotoMarchParams& p, const float* target, const float* cand0, const float* cand1, int idx0,
-                             const float* ident, const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H,
-                             int W, float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
-                             float* g_cand1, const uint8_t* region, float* g_region0, float* g_region1, const float* orig0,
-                             const float* orig1, size_t orig_stride, int target_texels, int weight_given);
-int photo_march_fused_more(const float* target, const float* cand0, const float* cand1, int idx0, const float* ident,
-                           const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H, int W,
-                           float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
-                           float* g_cand1, int* per_sample_out, hipStream_t st, const uint8_t* region, float* g_region0,
-                           float* g_region1, unsigned* order, unsigned* order_count, const float* orig0, const float* orig1,
-                           size_t orig_stride, int target_texels, int weight_given) {
+// The temporal hint of the whole-step list in ONE sweep (mal_march.h: FusedMoreArgs): the pair joins the running min
+// prev_min / prev_arg (read-only; must not alias the outputs), automask against ident (+ noise); the outputs min_reproj /
+// argmin / weight_out arrive holding the decision over the earlier candidates and are overwritten where this pair is
+// re-decided; per-task partials [task][2] = DIFFERENCES of sum(rp*w), sum(w) against that earlier decision; and
+// d sum(rp*w) / d candidate, unnormalised.  The checks and the kernel's parameter block of one sweep:
+static int fused_more_params(PhotoMarchParams& p, const FusedMoreArgs& x, int B, int H, int W) {
+  if (x.prev_min == x.min_reproj || x.prev_arg == x.argmin) return MAL_EINVAL;
+  if (x.weight_given && x.noise) return MAL_EINVAL;
+  if ((x.orig0 == nullptr) != (x.orig1 == nullptr) || (x.orig0 && !x.region)) return MAL_EINVAL;
+  if ((long long)B * 3 * H * W * 4 >= (1ll << 32)) return MAL_ESHAPE;  // (B,3,H,W) images are addressed with 32-bit byte offsets
+  const size_t orig_stride = x.orig_stride ? x.orig_stride : (size_t)3 * H * W;
+  if (x.orig0 && (long long)B * (long long)orig_stride * 4 >= (1ll << 32)) return MAL_ESHAPE;  // 32-bit byte offsets
+  p = PhotoMarchParams{};
+  p.target = x.target; p.target_texels = 1;  // the fused sweep reads the target as texels (compile-time in the kernel)
+  p.weight_given = x.weight_given; p.B = B; p.H = H; p.W = W;
+  p.cand[0] = x.cand0; p.cand[1] = x.cand1; p.idx[0] = x.idx0; p.idx[1] = x.idx0 + 1;
+  p.prev_min = x.prev_min; p.prev_arg = x.prev_arg; p.ident = x.ident; p.noise = x.noise;
+  p.min_reproj = x.min_reproj; p.argmin = x.argmin; p.weight_out = x.weight_out; p.block_sums = x.block_sums;
+  p.g_cand[0] = x.g_cand0; p.g_cand[1] = x.g_cand1; p.region = x.region;
+  p.orig[0] = x.orig0; p.orig[1] = x.orig1; p.orig_stride = orig_stride;
+  if (x.region && x.g_region0 && x.g_region1) { p.g_region[0] = x.g_region0; p.g_region[1] = x.g_region1; }
+  // with a region map the few tasks that do the full work set the kernel's duration (every task is resident at once, and
+  // a wavefront alone on its SIMD marches no faster): shorter tasks, four times as many (the workspace holds 2-row tasks)
+  if (x.region && g_syn_rows >= 2 && g_syn_rows < 8) decompose(p, 60, 8, g_syn_rows);
+  else decompose(p, 60, 2);
+  return MAL_OK;
+}
+// one sweep; order (nullable): >= ntasks device words, order_count: two zeroed words
+int photo_march_fused_more(const FusedMoreArgs& a, int B, int H, int W, int* per_sample_out, hipStream_t st, unsigned* order,
+                           unsigned* order_count) {
   PhotoMarchParams p = {};
-  int rc = fused_more_params(p, target, cand0, cand1, idx0, ident, noise, prev_min, prev_arg, B, H, W, min_reproj, argmin, weight_out,
-                             block_sums, g_cand0, g_cand1, region, g_region0, g_region1, orig0, orig1, orig_stride, target_texels,
-                             weight_given);
+  int rc = fused_more_params(p, a, B, H, W);
   if (rc) return rc;
   *per_sample_out = p.strips * p.segs;
   unsigned grid = (unsigned)p.per_xcd * 8u;
 #ifdef MAL_EXPERIMENTS
-  if (region && order && order_count && g_syn_queue) {  // expensive tasks first (see PhotoMarchParams::order)
+  if (a.region && order && order_count && g_syn_queue) {  // expensive tasks first (see PhotoMarchParams::order)
     p.order = order; p.order_count = order_count;
     grid = (unsigned)p.ntasks;
     hipLaunchKernelGGL(photo_march_classify_kernel, dim3(grid), dim3(64), 0, st, p);
@@ -783,56 +795,18 @@ int photo_march_fused_more(const float* target, const float* cand0, const float*
   return launch_status();
 }
 
-// n <= MAL_MS_MAX_SCALES fused sweeps of one shape in ONE launch (mal_march.h: FusedMoreArgs = the arguments above)
+// n <= MAL_MS_MAX_SCALES such sweeps of one shape in ONE launch
 int photo_march_fused_more_n(int n, const FusedMoreArgs* a, int B, int H, int W, int* per_sample_out, hipStream_t st) {
   if (n < 1 || n > MAL_MS_MAX_SCALES) return MAL_EINVAL;
   PhotoMarchBatch q = {};
   for (int k = 0; k < n; ++k) {
-    const FusedMoreArgs& x = a[k];
-    const int rc = fused_more_params(q.s[k], x.target, x.cand0, x.cand1, x.idx0, x.ident, x.noise, x.prev_min, x.prev_arg, B, H, W,
-                                     x.min_reproj, x.argmin, x.weight_out, x.block_sums, x.g_cand0, x.g_cand1, x.region, x.g_region0,
-                                     x.g_region1, x.orig0, x.orig1, x.orig_stride, 1, x.weight_given);
+    const int rc = fused_more_params(q.s[k], a[k], B, H, W);
     if (rc) return rc;
     if (q.s[k].ntasks != q.s[0].ntasks) return MAL_EINVAL;  // (a scale without a region map decomposes differently: not batched)
   }
   *per_sample_out = q.s[0].strips * q.s[0].segs;
   hipLaunchKernelGGL(photo_march_bwd_batch_kernel, dim3((unsigned)q.s[0].per_xcd * 8u, (unsigned)n), dim3(64), 0, st, q);
   return launch_status();
-}
-
-static int fused_more_params_impl(PhotoMarchParams& p, const float* target, const float* cand0, const float* cand1, int idx0,
-                                  const float* ident, const float* noise, const float* prev_min, const uint8_t* prev_arg, int B,
-                                  int H, int W, float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums,
-                                  float* g_cand0, float* g_cand1, const uint8_t* region, float* g_region0, float* g_region1,
-                                  const float* orig0, const float* orig1, size_t orig_stride, int target_texels, int weight_given) {
-  if (prev_min == min_reproj || prev_arg == argmin) return MAL_EINVAL;
-  if (weight_given && noise) return MAL_EINVAL;
-  if ((orig0 == nullptr) != (orig1 == nullptr) || (orig0 && !region)) return MAL_EINVAL;
-  if (!target_texels) return MAL_EINVAL;  // the fused sweep reads the target as texels (compile-time in the kernel)
-  if ((long long)B * 3 * H * W * 4 >= (1ll << 32)) return MAL_ESHAPE;  // (B,3,H,W) images are addressed with 32-bit byte offsets
-  if (orig0 && (long long)B * (long long)(orig_stride ? orig_stride : (size_t)3 * H * W) * 4 >= (1ll << 32)) return MAL_ESHAPE;  // 32-bit byte offsets
-  p = PhotoMarchParams{};
-  p.target = target; p.target_texels = target_texels; p.weight_given = weight_given; p.B = B; p.H = H; p.W = W;
-  p.cand[0] = cand0; p.cand[1] = cand1; p.idx[0] = idx0; p.idx[1] = idx0 + 1;
-  p.prev_min = prev_min; p.prev_arg = prev_arg; p.ident = ident; p.noise = noise;
-  p.min_reproj = min_reproj; p.argmin = argmin; p.weight_out = weight_out; p.block_sums = block_sums;
-  p.g_cand[0] = g_cand0; p.g_cand[1] = g_cand1; p.region = region;
-  p.orig[0] = orig0; p.orig[1] = orig1; p.orig_stride = orig_stride ? orig_stride : (size_t)3 * H * W;
-  if (region && g_region0 && g_region1) { p.g_region[0] = g_region0; p.g_region[1] = g_region1; }
-  // with a region map the few tasks that do the full work set the kernel's duration (every task is resident at once, and
-  // a wavefront alone on its SIMD marches no faster): shorter tasks, four times as many (the workspace holds 2-row tasks)
-  if (region && g_syn_rows >= 2 && g_syn_rows < 8) decompose(p, 60, 8, g_syn_rows); else
-  decompose(p, 60, 2);
-  return MAL_OK;
-}
-static int fused_more_params(PhotoMarchParams& p, const float* target, const float* cand0, const float* cand1, int idx0,
-                             const float* ident, const float* noise, const float* prev_min, const uint8_t* prev_arg, int B, int H,
-                             int W, float* min_reproj, uint8_t* argmin, float* weight_out, double* block_sums, float* g_cand0,
-                             float* g_cand1, const uint8_t* region, float* g_region0, float* g_region1, const float* orig0,
-                             const float* orig1, size_t orig_stride, int target_texels, int weight_given) {
-  return fused_more_params_impl(p, target, cand0, cand1, idx0, ident, noise, prev_min, prev_arg, B, H, W, min_reproj, argmin,
-                                weight_out, block_sums, g_cand0, g_cand1, region, g_region0, g_region1, orig0, orig1, orig_stride,
-                                target_texels, weight_given);
 }
 
 }  // namespace mal

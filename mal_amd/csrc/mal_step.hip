@@ -27,6 +27,31 @@ namespace mal {
 constexpr int kLossSlots = 16;
 constexpr int kEpiBlocks = 64;  // epilogue workgroups per sample in the final launch (their partials are summed in block order)
 
+// ---- the step's options (mal_set_option), with what was measured for each
+opt_t g_march_halo1{1};  // option "march_halo1": one-row halo of the step's gradient passes (0: two rows, A/B)
+opt_t g_step_overlap{1};  // option "step_overlap": a hinted step forks passes onto the library's side stream (side_stream, below)
+// option "temporal_spec" (--temporal step): 1 = the pass in front of the producer is the teacher's GRADIENT pass (it
+// exports the warped images as well) and the sweep after the producer's backward only corrects the tasks near the region
+// map; 0 = forward-only pass in front, full gradient sweep behind (rounds 2-3, kept for same-box A/B)
+opt_t g_temporal_spec{0};  // settable in -DMAL_EXPERIMENTS builds only (mal_set_option refuses it otherwise)
+// option "side_priority": 1 = the side stream is created with the device's LOWEST priority.  Measured: every kernel of the
+// replayed step slows down -- 0.566 ms per step against 0.323 (profiles/r04_step_timelines.txt) --, so the default stays 0.
+opt_t g_side_priority{0};
+// option "student_overlap": what is forked beside the producer: the ensemble pass (unless --no_ens) and, with it (default), the
+// student's marching pass without its epilogue; value 2 (default): the two as ONE launch that skips the augmented samples
+// (aug_skip_applies), 1: a launch each, every sample computed
+opt_t g_student_overlap{2};
+// option "side_order" 1: the student's pass first, the (lighter, forward-only) ensemble pass behind it -- the one that ends up
+// beside the fused sweep; 0: ensemble first.  1 measured slower: 0.3265 vs 0.3200 ms -- the producer's small kernels starve
+// beside a pass that holds every wave slot and all of the LDS
+opt_t g_side_order{0};
+// option "tail_overlap": 1 = a --temporal step's backward chain (producer's backward -> teacher's gradient sweep) runs on the
+// library's side stream behind the FUSED SWEEP only, beside the epilogue and the reduction of the forward (in a captured graph
+// the two chains are independent; eager: the same order as before, the side stream simply has nothing to wait for)
+opt_t g_tail_overlap{1};
+// option "sweeps_batched" (A/B): --temporal --main_temporal: the teacher's and the student's fused sweep as one launch
+opt_t g_sweeps_batched{1};
+
 struct StepWs {
   float* packed[3];   // target, src-1, src+1 as (B,H,W,kTexel) texels
   float* T[2]; float* gT[2]; float* gTs[2];
@@ -60,7 +85,7 @@ static StepWs carve_step(void* base, int B, int H, int W) {
   char* p = (char*)base;
   size_t o = 0;
   const size_t HW = (size_t)H * W, map = align256(B * HW * sizeof(float)), nb = ws_blocks(B, H, W);
-  auto take = [&](size_t bytes) { char* r = p + o; o += align256(bytes); return r; };
+  auto take = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align256(bytes); return r; };  // (null base: sizing only)
   for (int i = 0; i < 3; ++i) w.packed[i] = (float*)take(B * HW * kTexel * sizeof(float));
   for (int f = 0; f < 2; ++f) { w.T[f] = (float*)take(B * 16 * 4); w.gT[f] = (float*)take(B * 16 * 4); w.gTs[f] = (float*)take(B * 16 * 4); }
   float** maps[] = {&w.ident, &w.mono_reproj, &w.ens_reproj, &w.G_r_t, &w.G_r_s, &w.G_c,
@@ -402,11 +427,6 @@ __global__ __launch_bounds__(256) void step_assemble_kernel(StepAssemble p, Pose
   }
 }
 
-}  // namespace mal
-
-using namespace mal;
-
-namespace mal {
 // blockIdx.y = map k of `maps`: step number (counter ? *counter : step) * mult + k.  One thread per pixel GROUP (the four
 // rows (y & ~3) .. + 3 of a column share one Philox block): consecutive threads = consecutive columns
 struct NoiseMaps { float* out[4]; };
@@ -436,6 +456,8 @@ int tiebreak_noise_launch(unsigned long long seed, unsigned long long step, cons
 }
 }  // namespace mal
 
+using namespace mal;
+
 extern "C" int mal_tiebreak_noise(uint64_t seed, uint64_t step, int B, int H, int W, float* out, void* stream) {
   int rc = check_shape(B, H, W);
   if (rc) return rc;
@@ -448,11 +470,14 @@ extern "C" size_t mal_step_workspace_bytes(int B, int H, int W) {
   return carve_step(nullptr, B, H, W).bytes;
 }
 
-// MAL_STEP_TEXEL_INPUTS: the caller's three images ARE the (B,H,W,3) texel images (torch.channels_last): nothing is repacked
-static void use_texel_inputs(const mal_step_args* a, StepWs& w) {
+// the step's workspace; MAL_STEP_TEXEL_INPUTS: the caller's three images ARE the (B,H,W,3) texel images (torch.channels_last):
+// nothing is repacked
+static StepWs step_ws(const mal_step_args* a) {
+  StepWs w = carve_step(a->ws, a->B, a->H, a->W);
   if (a->flags & MAL_STEP_TEXEL_INPUTS) {
     w.packed[0] = const_cast<float*>(a->color0); w.packed[1] = const_cast<float*>(a->color_m1); w.packed[2] = const_cast<float*>(a->color_p1);
   }
+  return w;
 }
 
 static int step_check(const mal_step_args* a) {
@@ -477,14 +502,7 @@ static int step_check(const mal_step_args* a) {
 //    terms + the tie-break noise; B extra workgroups of the same launch: poses (frame -1 is inverted,
 //    networks/repdepth.py:159-160) + camera block
 static int first_sweep(const mal_step_args* a, const StepWs& w, hipStream_t st, int* per_sample_p) {
-  const int B = a->B, H = a->H, W = a->W;
-  StepPoses sp = {};
-  sp.pose.B = B; sp.pose.F = 2;
-  sp.pose.axisangle[0] = a->axisangle_m1; sp.pose.axisangle[1] = a->axisangle_p1;
-  sp.pose.translation[0] = a->translation_m1; sp.pose.translation[1] = a->translation_p1;
-  sp.pose.invert[0] = 1; sp.pose.invert[1] = 0;
-  sp.pose.T[0] = w.T[0]; sp.pose.T[1] = w.T[1];
-  sp.K = a->K; sp.invK = a->inv_K; sp.cam = w.cam; sp.ticket = w.ticket;
+  const StepPoses sp = step_poses(a, w.T, w.cam, w.ticket);
   TieNoise tn = {};
   if (a->flags & MAL_STEP_NOISE_PHILOX) {
     if (a->noise) return MAL_EINVAL;
@@ -495,19 +513,22 @@ static int first_sweep(const mal_step_args* a, const StepWs& w, hipStream_t st, 
   SmoothParams sm = {};
   sm.n = 2; sm.disp[0] = a->disp_teacher; sm.disp[1] = a->disp_student; sm.gn[0] = w.gn_t; sm.gn[1] = w.gn_s;
   sm.partials = w.bs_p; sm.dec[0] = a->dec_teacher; sm.dec[1] = a->dec_student;
-  const bool tex = (a->flags & MAL_STEP_TEXEL_INPUTS) != 0;
-  return pack_identity_launch(a->color0, a->color_m1, a->color_p1, B, H, W, tex ? nullptr : w.packed[1], tex ? nullptr : w.packed[2],
-                              tex ? nullptr : w.packed[0], w.ident, st, &sp, &tn, &sm, per_sample_p, tex);
+  PackIdentityArgs pk = {};
+  pk.target = a->color0; pk.src[0] = a->color_m1; pk.src[1] = a->color_p1; pk.ident = w.ident;
+  pk.texel_in = (a->flags & MAL_STEP_TEXEL_INPUTS) != 0;
+  if (!pk.texel_in) { pk.packed[0] = w.packed[1]; pk.packed[1] = w.packed[2]; pk.packed_target = w.packed[0]; }
+  pk.poses = &sp; pk.noise = &tn; pk.smooth = &sm;
+  return pack_identity_launch(pk, a->B, a->H, a->W, st, per_sample_p);
 }
 
-namespace mal { opt_t g_march_halo1{1}; }   // option "march_halo1": one-row halo of the step's gradient passes (0: two rows, A/B)
-
+// the block every marching pass of this step shares (the first launch filled the camera block)
+static MarchParams pass_params(const mal_step_args* a, const StepWs& w) {
+  return step_march_params(a, 0, w.T[0], w.T[1], w.packed, w.cam);
+}
 static MarchParams teacher_params(const mal_step_args* a, const StepWs& w, float* mono_reproj) {
-  MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, 0);
-  p.disp = a->disp_teacher; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
-  p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+  MarchParams p = pass_params(a, w);
+  p.disp = a->disp_teacher;
   p.min_reproj = mono_reproj; p.block_gP = w.bgP;
-  p.cam = w.cam; p.cam_ready = 1;  // the first launch filled the camera block
   return p;
 }
 
@@ -516,19 +537,17 @@ static int launch_teacher(const mal_step_args* a, const StepWs& w, float* mono_r
   MarchParams p = teacher_params(a, w, mono_reproj);
   p.ident = w.ident; p.noise = a->noise; p.g_reproj = w.G_r_t;
   p.block_sums = w.bs_t;
-  p.bnd = g_march_halo1 ? w.bnd_t : nullptr;
+  p.bnd = halo_bnd(w.bnd_t);
   p.dbg = a->dec_teacher;
   return march_launch(p, MAL_F_AUTOMASK | MAL_F_GRAD | MAL_F_POSE_GRAD | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
 }
 
 // the ensemble pass (no gradient): the averaged disparity is formed inside the kernel (trainer.py:594-600)
 static MarchParams ensemble_params(const mal_step_args* a, const StepWs& w, float* ens_reproj) {
-  MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, 0);
-  p.disp = a->disp_teacher; p.disp2 = a->disp_student; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
+  MarchParams p = pass_params(a, w);
+  p.disp = a->disp_teacher; p.disp2 = a->disp_student;
   if (a->ens_disp) { p.disp = a->ens_disp; p.disp2 = nullptr; }  // --learn_ens: the head's disparity (trainer.py:596-597)
-  p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
   p.min_reproj = ens_reproj; p.block_sums = w.bs_e; p.block_gP = w.bgP_e;
-  p.cam = w.cam; p.cam_ready = 1;
   return p;
 }
 static int launch_ensemble(const mal_step_args* a, const StepWs& w, float* ens_reproj, hipStream_t st) {
@@ -541,9 +560,8 @@ static int launch_ensemble(const mal_step_args* a, const StepWs& w, float* ens_r
 static MarchParams student_params(const mal_step_args* a, const StepWs& w, float* mono_reproj, float* ens_reproj, float* multi_reproj,
                                   bool epi) {
   const int B = a->B, H = a->H, W = a->W;
-  MarchParams p = march_params(B, H, W, a->min_depth, a->max_depth, 1e-7f, 0);
-  p.disp = a->disp_student; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
-  p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+  MarchParams p = pass_params(a, w);
+  p.disp = a->disp_student;
   p.ext_mask = a->consistency_mask; p.sample_scale = a->augmentation_keep;
   p.sample_scale_is_mask = (a->flags & MAL_STEP_AUG_MASK) ? 1 : 0;
   p.mono_disp = a->disp_teacher; p.lowest_cost = a->lowest_cost; p.cmask_out = a->consistency_mask_out;
@@ -556,8 +574,7 @@ static MarchParams student_params(const mal_step_args* a, const StepWs& w, float
     p.merge_cons = (float)((double)a->w_main / ((double)B * H * W)); p.merge_distil = (float)((double)a->w_distil / ((double)B * H * W));
   }
   p.block_sums = w.bs_s; p.block_gP = w.bgP_e;  // (no pose gradient in this pass: the sink is never written)
-  p.bnd = g_march_halo1 ? w.bnd_s : nullptr;
-  p.cam = w.cam; p.cam_ready = 1;
+  p.bnd = halo_bnd(w.bnd_s);
   p.dbg = a->dec_student;
   return p;
 }
@@ -572,9 +589,8 @@ static int launch_student(const mal_step_args* a, const StepWs& w, float* mono_r
 // candidates, its winner and the pass's weight (consistency x matching x (1 - augmentation): the four-way min does not change it)
 // stay in the workspace, with the sums, for mal_loss_step_fwd
 static int launch_student_warp(const mal_step_args* a, const StepWs& w, hipStream_t st) {
-  MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, 0);
-  p.disp = a->disp_student; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
-  p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+  MarchParams p = pass_params(a, w);
+  p.disp = a->disp_student;
   p.ext_mask = a->consistency_mask; p.sample_scale = a->augmentation_keep;
   p.sample_scale_is_mask = (a->flags & MAL_STEP_AUG_MASK) ? 1 : 0;
   p.mono_disp = a->disp_teacher; p.lowest_cost = a->lowest_cost; p.cmask_out = a->consistency_mask_out;
@@ -582,18 +598,15 @@ static int launch_student_warp(const mal_step_args* a, const StepWs& w, hipStrea
   p.argmin_out = w.arg_warp_s; p.argmin_out2 = w.arg_s; p.weight_out = w.w_s;
   p.color_out[0] = a->warp_s_m1; p.color_out[1] = a->warp_s_p1; p.color_out_stride = a->warp_sample_stride;
   p.block_sums = w.bs_s; p.block_gP = w.bgP_e;
-  p.cam = w.cam; p.cam_ready = 1;
   return march_launch(p, MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
 }
 // ... and its gradient sweep in mal_loss_step_bwd: the four-way decisions of _fwd, what arrives through syn added
 static int launch_student_temporal(const mal_step_args* a, const StepWs& w, hipStream_t st) {
-  MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, 0);
-  p.disp = a->disp_student; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
-  p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+  MarchParams p = pass_params(a, w);
+  p.disp = a->disp_student;
   p.g_reproj = w.G_r_s; p.block_sums = w.bs_e; p.block_gP = w.bgP_e;  // (the sums were taken by _fwd: a sink here)
   p.forced_w = w.w_s; p.forced_arg = w.arg_s; p.g_color[0] = a->g_warp_s_m1; p.g_color[1] = a->g_warp_s_p1;
-  p.bnd = g_march_halo1 ? w.bnd_s : nullptr;
-  p.cam = w.cam; p.cam_ready = 1;
+  p.bnd = halo_bnd(w.bnd_s);
   p.dbg = a->dec_student;
   return march_launch(p, MAL_F_GRAD | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
 }
@@ -617,12 +630,7 @@ static EpiParams epilogue_params(const mal_step_args* a, const StepWs& w, const 
 // Temporal hint: between the warp pass and the fused sweep the device runs the producer's small, latency-bound kernels
 // (and whatever the segmenter does) -- the ensemble pass depends on none of it.  It is forked onto a side stream AFTER the
 // warp pass (beside it, two ALU-bound passes only slow each other down: measured) and joined before the student pass,
-// which reads its map.  Fork / join through events: capturable into the caller's HIP graph.
-namespace mal { opt_t g_step_overlap{1}; }  // option "step_overlap"
-// option "temporal_spec" (--temporal step): 1 = the pass in front of the producer is the teacher's GRADIENT pass (it
-// exports the warped images as well) and the sweep after the producer's backward only corrects the tasks near the region
-// map; 0 = forward-only pass in front, full gradient sweep behind (rounds 2-3, kept for same-box A/B)
-namespace mal { opt_t g_temporal_spec{0}; }  // settable in -DMAL_EXPERIMENTS builds only (mal_set_option refuses it otherwise)
+// which reads its map.  Fork / join through events: capturable into the caller's HIP graph (option "step_overlap").
 // One side stream (with its fork / join events) per (device, caller stream): two steps in flight on different streams of a
 // device -- each with its own workspace -- then cannot consume or overwrite each other's pending join (round 3 kept one
 // `pending` flag per device: step B's _warp cleared A's, and B's _fwd could return without waiting for its own ensemble
@@ -630,9 +638,6 @@ namespace mal { opt_t g_temporal_spec{0}; }  // settable in -DMAL_EXPERIMENTS bu
 // caller stream that finds it full shares slot 0 of its device, and every _fwd of a forked step waits for the slot's join
 // event whatever `pending` says, so sharing costs ordering, never correctness.  Lookups are serialised by a mutex; the
 // launches themselves are the caller's (one thread per stream, as for every HIP stream).
-// option "side_priority": 1 = the side stream is created with the device's LOWEST priority.  Measured: every kernel of the
-// replayed step slows down -- 0.566 ms per step against 0.323 (profiles/r04_step_timelines.txt) --, so the default stays 0.
-namespace mal { opt_t g_side_priority{0}; }
 // sweep / tail (option "tail_overlap"): `sweep` is recorded on the caller's stream behind the fused sweep of a --temporal step;
 // the producer's backward and the teacher's gradient sweep then run on the side stream behind it -- beside the epilogue and the
 // reduction, which the caller's stream runs meanwhile -- and `tail` joins them back in front of the assembly
@@ -719,16 +724,6 @@ int side_end(hipStream_t st) {
 }
 int side_wait(hipStream_t st, bool always) { return join_side(st, always); }
 }
-// what is forked beside the producer: the ensemble pass (unless --no_ens) and, with option "student_overlap" (default), the
-// student's marching pass without its epilogue; value 2 (default): the two as ONE launch that skips the augmented samples
-// (aug_skip_applies), 1: a launch each, every sample computed
-namespace mal { opt_t g_student_overlap{2}; opt_t g_side_order{0}; }
-// option "tail_overlap": 1 = a --temporal step's backward chain (producer's backward -> teacher's gradient sweep) runs on the
-// library's side stream behind the FUSED SWEEP only, beside the epilogue and the reduction of the forward (in a captured graph
-// the two chains are independent; eager: the same order as before, the side stream simply has nothing to wait for)
-namespace mal { opt_t g_tail_overlap{1}; }
-// option "sweeps_batched" (A/B): --temporal --main_temporal: the teacher's and the student's fused sweep as one launch
-namespace mal { opt_t g_sweeps_batched{1}; }
 static bool tail_applies(const mal_step_args* a) {
   return g_tail_overlap && g_step_overlap == 1 && !g_temporal_spec && (a->flags & (MAL_STEP_TEMPORAL | MAL_STEP_MAIN_TEMPORAL)) &&
          side_stream((hipStream_t)a->stream) != nullptr;
@@ -753,7 +748,7 @@ extern "C" int mal_loss_step_tail_cancel(const mal_step_args* a) {
   if (!a) return MAL_EINVAL;
   SideStream* ss = side_stream((hipStream_t)a->stream);
   return join_tail(ss, (hipStream_t)a->stream);
-}  // side_order 1 (student first) measured slower: 0.3265 vs 0.3200 ms -- the producer's small kernels starve beside a pass that holds every wave slot and all of the LDS
+}
 static bool side_forked(const mal_step_args* a) {
   return g_step_overlap && (a->flags & (MAL_STEP_TEMPORAL | MAL_STEP_MAIN_TEMPORAL)) && side_stream((hipStream_t)a->stream) != nullptr;
 }
@@ -781,11 +776,6 @@ static bool aug_skip_applies(const mal_step_args* a) {
          student_forked(a) && !a->ens_disp && a->augmentation_keep && !a->multi_reproj && !a->ens_reproj &&
          !a->consistency_mask_out && !a->dec_student && march_pair_qualifies(a->B, a->H, a->W);
 }
-static int launch_forked_pair(const mal_step_args* a, const StepWs& w, hipStream_t st) {
-  MarchParams stu = student_params(a, w, nullptr, nullptr, w.multi_reproj, false);
-  MarchParams ens = ensemble_params(a, w, w.ens_reproj);
-  return march_pair_launch(ensemble_forked(a) ? &ens : nullptr, stu, g_side_order ? 1 : 0, st);
-}
 
 static int fork_ensemble(const mal_step_args* a, const StepWs& w, hipStream_t st) {
   SideStream* ss = side_stream(st);
@@ -796,19 +786,17 @@ static int fork_ensemble(const mal_step_args* a, const StepWs& w, hipStream_t st
     rc = launch_student_warp(a, w, ss->s);
     if (hipEventRecord(ss->mid, ss->s) != hipSuccess && !rc) rc = MAL_ELAUNCH;
   }
-  // option "side_order" 1: the student's pass first, the (lighter, forward-only) ensemble pass behind it -- the one that ends up
-  // beside the fused sweep; 0: ensemble first
+  auto student = [&]() {
+    return launch_student(a, w, nullptr, nullptr, a->multi_reproj ? a->multi_reproj : w.multi_reproj, false, ss->s, nullptr);
+  };
   if (aug_skip_applies(a)) {  // both forked passes in one launch, augmented samples skipped
-    rc = launch_forked_pair(a, w, ss->s);
-    if (hipEventRecord(ss->join, ss->s) != hipSuccess) return rc ? rc : MAL_ELAUNCH;
-    ss->pending = true;
-    return rc;
+    MarchParams stu = student_params(a, w, nullptr, nullptr, w.multi_reproj, false), ens = ensemble_params(a, w, w.ens_reproj);
+    rc = march_pair_launch(ensemble_forked(a) ? &ens : nullptr, stu, g_side_order ? 1 : 0, ss->s);
+  } else {
+    if (g_side_order && student_forked(a)) rc = student();
+    if (!rc && ensemble_forked(a)) rc = launch_ensemble(a, w, a->ens_reproj ? a->ens_reproj : w.ens_reproj, ss->s);
+    if (!rc && !g_side_order && student_forked(a)) rc = student();
   }
-  if (g_side_order && student_forked(a))
-    rc = launch_student(a, w, nullptr, nullptr, a->multi_reproj ? a->multi_reproj : w.multi_reproj, false, ss->s, nullptr);
-  if (!rc && ensemble_forked(a)) rc = launch_ensemble(a, w, a->ens_reproj ? a->ens_reproj : w.ens_reproj, ss->s);
-  if (!rc && !g_side_order && student_forked(a))
-    rc = launch_student(a, w, nullptr, nullptr, a->multi_reproj ? a->multi_reproj : w.multi_reproj, false, ss->s, nullptr);
   if (hipEventRecord(ss->join, ss->s) != hipSuccess) return rc ? rc : MAL_ELAUNCH;
   ss->pending = true;  // whatever was enqueued on the side stream is joined before the step's buffers are reused
   return rc;
@@ -835,24 +823,8 @@ extern "C" int mal_loss_step_student_ready(const mal_step_args* a) {
 
 // MAL_STEP_TEMPORAL, first call: the first sweep and the teacher's warped images (forward only: the per-pixel min over
 // the two warped candidates and its winner stay in the workspace for mal_loss_step_fwd)
-extern "C" int mal_loss_step_warp(const mal_step_args* a) {
-  int rc = step_check(a);
-  if (rc) return rc;
-  const bool temporal = a->flags & MAL_STEP_TEMPORAL, main_t = a->flags & MAL_STEP_MAIN_TEMPORAL;
-  if (!temporal && !main_t) return MAL_EINVAL;
-  if (temporal && (!a->warp_m1 || !a->warp_p1)) return MAL_EINVAL;
-  if (main_t && (!a->warp_s_m1 || !a->warp_s_p1)) return MAL_EINVAL;
-  if ((a->warp2_m1 == nullptr) != (a->warp2_p1 == nullptr)) return MAL_EINVAL;
-  StepWs w = carve_step(a->ws, a->B, a->H, a->W);
-  use_texel_inputs(a, w);
-  hipStream_t st = (hipStream_t)a->stream;
-  rc = join_side(st);  // a previous step that was abandoned after its fork (no _fwd, no _abort)
-  if (rc) return rc;
-  step_geom_record(a->ws, a->B, a->H, a->W);
-  int per_sample_p = 1;
-  rc = first_sweep(a, w, st, &per_sample_p);
-  if (rc) return rc;
-  if (temporal) {
+// the teacher's forward pass in front of the producer: the warped images out, the min over the two warped candidates and its winner
+static int launch_teacher_warp(const mal_step_args* a, const StepWs& w, hipStream_t st) {
   MarchParams p = teacher_params(a, w, w.rp_warp);
   p.block_sums = w.bs_t;
   // ... with the automask: where no synthesised candidate can win, this IS the teacher's forward (min, winner, weight,
@@ -864,25 +836,38 @@ extern "C" int mal_loss_step_warp(const mal_step_args* a) {
     // so the map, boundary rows and pose partials this pass leaves are final there (mal_loss_step_bwd redoes the rest)
     flags |= MAL_F_GRAD | MAL_F_POSE_GRAD;
     p.g_reproj = w.G_r_t;
-    p.bnd = g_march_halo1 ? w.bnd_t : nullptr;
+    p.bnd = halo_bnd(w.bnd_t);
     p.dbg = a->dec_teacher;
   }
   p.min_reproj2 = a->mono_reproj ? a->mono_reproj : w.mono_reproj; p.argmin_out2 = w.arg_t; p.weight_out = w.w_t;
   p.color_out[0] = a->warp_m1; p.color_out[1] = a->warp_p1; p.argmin_out = w.arg_warp;
   p.color_out_stride = a->warp_sample_stride;
   p.color_out2[0] = a->warp2_m1; p.color_out2[1] = a->warp2_p1;
-  rc = march_launch(p, flags, st);
+  return march_launch(p, flags, st);
+}
+static int step_warp_body(const mal_step_args* a, const StepWs& w, hipStream_t st) {
+  int rc = join_side(st);  // a previous step that was abandoned after its fork (no _fwd, no _abort)
   if (rc) return rc;
-  }
-  if (main_t && !student_warp_forked(a)) {
-    rc = launch_student_warp(a, w, st);
-    if (rc) return rc;
-  }
-  if ((ensemble_forked(a) || student_forked(a) || student_warp_forked(a)) && g_step_overlap == 1) {
-    rc = fork_ensemble(a, w, st);
-    if (rc) return rc;
-  }
-  return MAL_OK;
+  step_geom_record(a->ws, a->B, a->H, a->W);
+  int per_sample_p = 1;
+  rc = first_sweep(a, w, st, &per_sample_p);
+  if (!rc && (a->flags & MAL_STEP_TEMPORAL)) rc = launch_teacher_warp(a, w, st);
+  if (!rc && (a->flags & MAL_STEP_MAIN_TEMPORAL) && !student_warp_forked(a)) rc = launch_student_warp(a, w, st);
+  if (!rc && (ensemble_forked(a) || student_forked(a) || student_warp_forked(a)) && g_step_overlap == 1) rc = fork_ensemble(a, w, st);
+  return rc;
+}
+extern "C" int mal_loss_step_warp(const mal_step_args* a) {
+  int rc = step_check(a);
+  if (rc) return rc;
+  const bool temporal = a->flags & MAL_STEP_TEMPORAL, main_t = a->flags & MAL_STEP_MAIN_TEMPORAL;
+  if (!temporal && !main_t) return MAL_EINVAL;
+  if (temporal && (!a->warp_m1 || !a->warp_p1)) return MAL_EINVAL;
+  if (main_t && (!a->warp_s_m1 || !a->warp_s_p1)) return MAL_EINVAL;
+  if ((a->warp2_m1 == nullptr) != (a->warp2_p1 == nullptr)) return MAL_EINVAL;
+  const StepWs w = step_ws(a);
+  rc = step_warp_body(a, w, (hipStream_t)a->stream);
+  if (rc) (void)join_side((hipStream_t)a->stream);  // the one exit: nothing of a failed call stays on the side stream
+  return rc;
 }
 
 // --distil with sclm > 0 and the temporal hint: the full-resolution warps of scales 1..sclm of every hinted pass, what the
@@ -913,147 +898,168 @@ extern "C" int mal_loss_step_warp_scales(const mal_step_args* a, const mal_step_
   }
   rc = step_check(a);
   if (rc) return rc;
-  StepWs w = carve_step(a->ws, a->B, a->H, a->W);
-  use_texel_inputs(a, w);
+  const StepWs w = step_ws(a);
   const float* src[2] = {w.packed[1], w.packed[2]};
   return warp_scales_launch(m, src, w.cam, a->B, a->H, a->W, a->min_depth, a->max_depth, a->warp_sample_stride,
                             (hipStream_t)a->stream);
 }
 
-extern "C" int mal_loss_step_fwd(const mal_step_args* a) {
-  int rc = step_check(a);
-  if (rc) return rc;
-  const int B = a->B, H = a->H, W = a->W;
-  StepWs w = carve_step(a->ws, B, H, W);
-  use_texel_inputs(a, w);
-  hipStream_t st = (hipStream_t)a->stream;
-  const bool no_ens = a->flags & MAL_STEP_NO_ENS, temporal = a->flags & MAL_STEP_TEMPORAL,
-             main_t = a->flags & MAL_STEP_MAIN_TEMPORAL, hinted = temporal || main_t;
-  float* mono_reproj = a->mono_reproj ? a->mono_reproj : w.mono_reproj;
-  float* ens_reproj = no_ens ? nullptr : (a->ens_reproj ? a->ens_reproj : w.ens_reproj);
-  float* multi_reproj = a->multi_reproj;  // only written when the caller wants the map
-  if (!hinted) step_geom_record(a->ws, B, H, W);
-  else if (step_geom_check(a->ws, B, H, W)) { (void)join_side(st); return MAL_ESTALE; }  // options changed after _warp
+// The fused sweep over the teacher's synthesised pair: mal_loss_step_warp left min_f r(warp_f) / its winner in rp_warp /
+// arg_warp; the two synthesised images join the running min (first minimum wins, as torch.min over [warp-1, warp+1, syn-1,
+// syn+1], loss_utils.py:79-90,103), the automask and the teacher's sums are formed over all four, and the gradient w.r.t. the
+// synthesised images leaves unnormalised.  MAL_STEP_SYN_SPARSE: syn_* hold the synthesised images at the region pixels only;
+// elsewhere they are the warped images mal_loss_step_warp wrote (warp_*), which the sweep then reads instead
+static FusedMoreArgs teacher_sweep(const mal_step_args* a, const StepWs& w, float* mono_reproj) {
+  const bool sparse = (a->flags & MAL_STEP_SYN_SPARSE) != 0;
+  FusedMoreArgs x = {};
+  x.target = w.packed[0]; x.cand0 = a->syn_m1; x.cand1 = a->syn_p1; x.idx0 = 2; x.ident = w.ident; x.noise = a->noise;
+  x.prev_min = w.rp_warp; x.prev_arg = w.arg_warp; x.min_reproj = mono_reproj; x.argmin = w.arg_t; x.weight_out = w.w_t;
+  x.block_sums = w.bs_ph; x.g_cand0 = a->g_syn_m1; x.g_cand1 = a->g_syn_p1; x.region = a->syn_region;
+  x.g_region0 = a->g_syn_region_m1; x.g_region1 = a->g_syn_region_p1;
+  x.orig0 = sparse ? a->warp_m1 : nullptr; x.orig1 = sparse ? a->warp_p1 : nullptr; x.orig_stride = (size_t)a->warp_sample_stride;
+  return x;
+}
+// --main_temporal: the student's pair joins ITS running min the same way; the weight is the pass's mask (w_s), whatever wins
+static FusedMoreArgs student_sweep(const mal_step_args* a, const StepWs& w) {
+  const bool sparse = (a->flags & MAL_STEP_SYN_S_SPARSE) != 0;
+  FusedMoreArgs x = {};
+  x.target = w.packed[0]; x.cand0 = a->syn_s_m1; x.cand1 = a->syn_s_p1; x.idx0 = 2;
+  x.ident = w.w_s; x.weight_given = 1;  // `ident` is the weight
+  x.prev_min = w.rp_warp_s; x.prev_arg = w.arg_warp_s; x.min_reproj = a->multi_reproj ? a->multi_reproj : w.multi_reproj;
+  x.argmin = w.arg_s; x.weight_out = w.w_s; x.block_sums = w.bs_sh; x.g_cand0 = a->g_syn_s_m1; x.g_cand1 = a->g_syn_s_p1;
+  x.region = a->syn_s_region; x.g_region0 = a->g_syn_s_region_m1; x.g_region1 = a->g_syn_s_region_p1;
+  x.orig0 = sparse ? a->warp_s_m1 : nullptr; x.orig1 = sparse ? a->warp_s_p1 : nullptr; x.orig_stride = (size_t)a->warp_sample_stride;
+  return x;
+}
+// the operands a sweep cannot do without (`sparse`: orig0 / orig1 are the caller's warped images; the launch checks the rest)
+static int sweep_check(const FusedMoreArgs& x, bool sparse) {
+  if (!x.cand0 || !x.cand1 || !x.g_cand0 || !x.g_cand1) return MAL_EINVAL;
+  if (sparse && (!x.region || !x.orig0 || !x.orig1)) return MAL_EINVAL;
+  return MAL_OK;
+}
 
-  int per_sample_p = 1, per_sample_ph = 0;
-  int per_sample = 1, per_sample_t = 0;
-  bool both_sweeps = false;
-  {  // tasks per sample of the teacher's sums: its gradient pass, or (temporal hint) the forward pass in front of the producer
-    int strips = 0, segs = 0;
-    march_geometry(B, H, W, temporal && !g_temporal_spec ? 0 : MAL_F_GRAD, &strips, &segs, nullptr);
-    per_sample_t = strips * segs;
-  }
-  if (hinted && ensemble_forked(a) && g_step_overlap == 2) {  // option "step_overlap" 2: the ensemble pass beside the sweeps of this call
-    rc = fork_ensemble(a, w, st);
+// ---- mal_loss_step_fwd, in stages; what they hand on:
+struct StepFwd {
+  bool no_ens, temporal, main_t, hinted;
+  float* mono_reproj; float* ens_reproj;
+  int per_sample_p, per_sample_ph, per_sample_sh, per_sample, per_sample_t;
+  bool stu_deferred;  // the student's marching pass has run: its epilogue is a launch of its own
+};
+// what does not wait for a fused sweep: the decomposition's check, the ensemble pass of option "step_overlap" 2, and -- the
+// teacher without the hint -- the first sweep (unless mal_loss_step_warp ran it) and its pass, forward and gradient in one sweep
+static int fwd_front(const mal_step_args* a, const StepWs& w, hipStream_t st, StepFwd& f) {
+  const int B = a->B, H = a->H, W = a->W;
+  if (!f.hinted) step_geom_record(a->ws, B, H, W);
+  else if (step_geom_check(a->ws, B, H, W)) return MAL_ESTALE;  // options changed after _warp
+  // tasks per sample of the teacher's sums: its gradient pass, or (temporal hint) the forward pass in front of the producer
+  f.per_sample_t = march_tasks_per_sample(B, H, W, f.temporal && !g_temporal_spec ? 0 : MAL_F_GRAD);
+  if (f.hinted) f.per_sample_p = pack_identity_tasks_per_sample(H, W);  // (mal_loss_step_warp ran the first sweep)
+  if (f.hinted && ensemble_forked(a) && g_step_overlap == 2) {  // the ensemble pass beside the sweeps of this call
+    const int rc = fork_ensemble(a, w, st);
     if (rc) return rc;
   }
-  if (!temporal) {
-    if (main_t) per_sample_p = pack_identity_tasks_per_sample(H, W);  // (mal_loss_step_warp ran the first sweep)
-    else rc = first_sweep(a, w, st, &per_sample_p);
+  if (f.temporal) return MAL_OK;
+  if (!f.hinted)
+    if (const int rc = first_sweep(a, w, st, &f.per_sample_p)) return rc;
+  return launch_teacher(a, w, f.mono_reproj, st);
+}
+// the fused sweeps of the hint: the teacher's, the student's (--main_temporal), or both as ONE launch (region-gated: a few
+// short tasks each)
+static int fwd_sweeps(const mal_step_args* a, const StepWs& w, hipStream_t st, StepFwd& f) {
+  const int B = a->B, H = a->H, W = a->W;
+  FusedMoreArgs fa[2] = {};
+  bool both = false;
+  int rc = MAL_OK;
+  if (f.temporal) {
+    fa[0] = teacher_sweep(a, w, f.mono_reproj);
+    rc = sweep_check(fa[0], (a->flags & MAL_STEP_SYN_SPARSE) != 0);
     if (rc) return rc;
-    // teacher pass: forward and gradient in one sweep
-    rc = launch_teacher(a, w, mono_reproj, st);
-    if (rc) { if (main_t) (void)join_side(st); return rc; }
-  } else {
-    // mal_loss_step_warp ran the first sweep and left min_f r(warp_f) / its winner in rp_warp / arg_warp: the two
-    // synthesised images join the running min (first minimum wins, as torch.min over [warp-1, warp+1, syn-1, syn+1],
-    // loss_utils.py:79-90,103), the automask and the teacher's sums are formed over all four, and the gradient w.r.t.
-    // the synthesised images leaves unnormalised
-    if (!a->syn_m1 || !a->syn_p1 || !a->g_syn_m1 || !a->g_syn_p1) { (void)join_side(st); return MAL_EINVAL; }
-    // MAL_STEP_SYN_SPARSE: syn_* hold the synthesised images at the region pixels only; elsewhere they are the warped
-    // images mal_loss_step_warp wrote (warp_*), which the sweep then reads instead
-    const bool sparse = (a->flags & MAL_STEP_SYN_SPARSE) != 0;
-    if (sparse && (!a->syn_region || !a->warp_m1 || !a->warp_p1)) { (void)join_side(st); return MAL_EINVAL; }
-    per_sample_p = pack_identity_tasks_per_sample(H, W);
-    // with --main_temporal too, both passes' sweeps (region-gated: a few short tasks each) go out as ONE launch, below
-    both_sweeps = main_t && g_sweeps_batched && a->syn_region && a->syn_s_region;
-    if (!both_sweeps)
-    rc = photo_march_fused_more(w.packed[0], a->syn_m1, a->syn_p1, 2, w.ident, a->noise, w.rp_warp, w.arg_warp, B, H, W,
-                                mono_reproj, w.arg_t, w.w_t, w.bs_ph, a->g_syn_m1, a->g_syn_p1, &per_sample_ph, st, a->syn_region,
-                                a->g_syn_region_m1, a->g_syn_region_p1, w.order, w.ticket + 1,
-                                sparse ? a->warp_m1 : nullptr, sparse ? a->warp_p1 : nullptr, (size_t)a->warp_sample_stride,
-                                1 /* the target as texels: one 12-byte load instead of three planes */, 0);
-    if (rc) { (void)join_side(st); return rc; }
+    both = f.main_t && g_sweeps_batched && a->syn_region && a->syn_s_region;
+    if (!both) rc = photo_march_fused_more(fa[0], B, H, W, &f.per_sample_ph, st, w.order, w.ticket + 1);
+    if (rc) return rc;
   }
-  int per_sample_sh = 0;
-  if (main_t && both_sweeps) {
-    if (!a->syn_s_m1 || !a->syn_s_p1 || !a->g_syn_s_m1 || !a->g_syn_s_p1) { (void)join_side(st); return MAL_EINVAL; }
-    const bool sp_t = (a->flags & MAL_STEP_SYN_SPARSE) != 0, sp_s = (a->flags & MAL_STEP_SYN_S_SPARSE) != 0;
-    if (sp_s && (!a->warp_s_m1 || !a->warp_s_p1)) { (void)join_side(st); return MAL_EINVAL; }
-    FusedMoreArgs fa[2] = {};
-    fa[0].target = w.packed[0]; fa[0].cand0 = a->syn_m1; fa[0].cand1 = a->syn_p1; fa[0].idx0 = 2; fa[0].ident = w.ident; fa[0].noise = a->noise;
-    fa[0].prev_min = w.rp_warp; fa[0].prev_arg = w.arg_warp; fa[0].min_reproj = mono_reproj; fa[0].argmin = w.arg_t; fa[0].weight_out = w.w_t;
-    fa[0].block_sums = w.bs_ph; fa[0].g_cand0 = a->g_syn_m1; fa[0].g_cand1 = a->g_syn_p1; fa[0].region = a->syn_region;
-    fa[0].g_region0 = a->g_syn_region_m1; fa[0].g_region1 = a->g_syn_region_p1;
-    fa[0].orig0 = sp_t ? a->warp_m1 : nullptr; fa[0].orig1 = sp_t ? a->warp_p1 : nullptr; fa[0].orig_stride = (size_t)a->warp_sample_stride;
-    fa[1].target = w.packed[0]; fa[1].cand0 = a->syn_s_m1; fa[1].cand1 = a->syn_s_p1; fa[1].idx0 = 2; fa[1].ident = w.w_s; fa[1].noise = nullptr;
-    fa[1].prev_min = w.rp_warp_s; fa[1].prev_arg = w.arg_warp_s; fa[1].min_reproj = a->multi_reproj ? a->multi_reproj : w.multi_reproj;
-    fa[1].argmin = w.arg_s; fa[1].weight_out = w.w_s; fa[1].block_sums = w.bs_sh; fa[1].g_cand0 = a->g_syn_s_m1; fa[1].g_cand1 = a->g_syn_s_p1;
-    fa[1].region = a->syn_s_region; fa[1].g_region0 = a->g_syn_s_region_m1; fa[1].g_region1 = a->g_syn_s_region_p1;
-    fa[1].orig0 = sp_s ? a->warp_s_m1 : nullptr; fa[1].orig1 = sp_s ? a->warp_s_p1 : nullptr; fa[1].orig_stride = (size_t)a->warp_sample_stride;
-    fa[1].weight_given = 1;  // `ident` is the weight
-    int per = 0;
-    rc = photo_march_fused_more_n(2, fa, B, H, W, &per, st);
-    if (rc) { (void)join_side(st); return rc; }
-    per_sample_ph = per_sample_sh = per;
-  } else if (main_t) {
-    // --main_temporal: the student's pair joins ITS running min the same way; the weight is the pass's mask (w_s), whatever wins
-    if (!a->syn_s_m1 || !a->syn_s_p1 || !a->g_syn_s_m1 || !a->g_syn_s_p1) { (void)join_side(st); return MAL_EINVAL; }
-    const bool sparse = (a->flags & MAL_STEP_SYN_S_SPARSE) != 0;
-    if (sparse && (!a->syn_s_region || !a->warp_s_m1 || !a->warp_s_p1)) { (void)join_side(st); return MAL_EINVAL; }
-    rc = photo_march_fused_more(w.packed[0], a->syn_s_m1, a->syn_s_p1, 2, w.w_s, nullptr, w.rp_warp_s, w.arg_warp_s, B, H, W,
-                                a->multi_reproj ? a->multi_reproj : w.multi_reproj, w.arg_s, w.w_s, w.bs_sh, a->g_syn_s_m1,
-                                a->g_syn_s_p1, &per_sample_sh, st, a->syn_s_region, a->g_syn_s_region_m1, a->g_syn_s_region_p1,
-                                nullptr, nullptr, sparse ? a->warp_s_m1 : nullptr, sparse ? a->warp_s_p1 : nullptr,
-                                (size_t)a->warp_sample_stride, 1, 1 /* `ident` is the weight */);
-    if (rc) { (void)join_side(st); return rc; }
+  if (f.main_t) {
+    fa[1] = student_sweep(a, w);
+    rc = sweep_check(fa[1], (a->flags & MAL_STEP_SYN_S_SPARSE) != 0);
+    if (rc) return rc;
+    if (both) {
+      int per = 0;
+      rc = photo_march_fused_more_n(2, fa, B, H, W, &per, st);
+      f.per_sample_ph = f.per_sample_sh = per;
+    } else {
+      rc = photo_march_fused_more(fa[1], B, H, W, &f.per_sample_sh, st);
+    }
+    if (rc) return rc;
   }
-  if (hinted) {  // what the backward chain waits for (mal_loss_step_tail_begin): the last fused sweep
+  if (f.hinted) {  // what the backward chain waits for (mal_loss_step_tail_begin): the last fused sweep
     SideStream* ss = g_step_overlap ? side_stream(st) : nullptr;
     if (ss) ss->sweep_valid = tail_applies(a) && hipEventRecord(ss->sweep, st) == hipSuccess;
     (void)hipGetLastError();
   }
-  // ensemble pass (no gradient); with the temporal hint it was forked beside the producer by mal_loss_step_warp -- and so
-  // was the student's marching pass (without its epilogue)
-  const bool ens_forked = hinted && ensemble_forked(a), stu_forked = temporal && student_forked(a);
-  const bool stu_deferred = stu_forked || main_t;  // the student's marching pass has run: its epilogue is a launch of its own
-  EpiParams epi = {};
-  if (ens_forked || stu_forked || (hinted && student_warp_forked(a))) {
-    rc = join_side(st, true);
+  return MAL_OK;
+}
+// the joins of the forked passes: with the temporal hint mal_loss_step_warp forked the ensemble pass (no gradient) beside the
+// producer -- and the student's marching pass (without its epilogue); what was not forked runs here
+static int fwd_join(const mal_step_args* a, const StepWs& w, hipStream_t st, StepFwd& f) {
+  const bool ens_forked = f.hinted && ensemble_forked(a), stu_forked = f.temporal && student_forked(a);
+  f.stu_deferred = stu_forked || f.main_t;
+  if (ens_forked || stu_forked || (f.hinted && student_warp_forked(a))) {
+    const int rc = join_side(st, true);
     if (rc) return rc;
   }
-  if (!no_ens && !ens_forked) {
-    rc = launch_ensemble(a, w, ens_reproj, st);
-    if (rc) return rc;
-  }
-  if (stu_deferred) {
-    // the student's pass ran beside the producer: its consistency / distillation terms now, from the three per-pixel minima
-    int strips = 0, segs = 0;
-    march_geometry(B, H, W, main_t ? 0 : MAL_F_GRAD, &strips, &segs, nullptr);  // the pass that left the student's sums
-    per_sample = strips * segs;
-    epi = epilogue_params(a, w, mono_reproj, ens_reproj, a->multi_reproj ? a->multi_reproj : w.multi_reproj);
-    hipLaunchKernelGGL(step_epilogue_kernel, dim3((unsigned)(B * kEpiBlocks)), dim3(256), 0, st, epi);
-    rc = launch_status();
-    if (rc) return rc;
-  } else {
-    // student pass with the consistency / distillation epilogue
-    rc = launch_student(a, w, mono_reproj, ens_reproj, multi_reproj, true, st, &per_sample);
-    if (rc) return rc;
-  }
-  // per-sample sums of both gradient passes, pose gradients (temporal: in _bwd, after the teacher's sweep), scalars
+  if (!f.no_ens && !ens_forked) return launch_ensemble(a, w, f.ens_reproj, st);
+  return MAL_OK;
+}
+// the student: its pass with the consistency / distillation epilogue, or -- the pass ran beside the producer -- those terms
+// now, from the three per-pixel minima
+static int fwd_student(const mal_step_args* a, const StepWs& w, hipStream_t st, StepFwd& f) {
+  if (!f.stu_deferred)  // (multi_reproj: only written when the caller wants the map)
+    return launch_student(a, w, f.mono_reproj, f.ens_reproj, a->multi_reproj, true, st, &f.per_sample);
+  f.per_sample = march_tasks_per_sample(a->B, a->H, a->W, f.main_t ? 0 : MAL_F_GRAD);  // the pass that left the student's sums
+  const EpiParams epi = epilogue_params(a, w, f.mono_reproj, f.ens_reproj, a->multi_reproj ? a->multi_reproj : w.multi_reproj);
+  hipLaunchKernelGGL(step_epilogue_kernel, dim3((unsigned)(a->B * kEpiBlocks)), dim3(256), 0, st, epi);
+  return launch_status();
+}
+// per-sample sums of both gradient passes, pose gradients (temporal: in _bwd, after the teacher's sweep), scalars
+static int fwd_reduce(const mal_step_args* a, const StepWs& w, hipStream_t st, StepFwd& f) {
+  const int B = a->B;
   StepFinal fin = {};
-  fin.bs_t = w.bs_t; fin.bs_s = w.bs_s; fin.bgP = temporal ? nullptr : w.bgP;
-  fin.bs_p = w.bs_p; fin.per_sample_p = per_sample_p;
-  fin.bs_ph = temporal ? w.bs_ph : nullptr; fin.per_sample_ph = per_sample_ph;
-  fin.bs_sh = main_t ? w.bs_sh : nullptr; fin.per_sample_sh = per_sample_sh;
-  fin.bs_d = stu_deferred ? w.bs_d : nullptr;
-  fin.K = a->K; fin.per_sample = per_sample; fin.per_sample_t = per_sample_t; fin.B = B; fin.H = H; fin.W = W;
+  fin.bs_t = w.bs_t; fin.bs_s = w.bs_s; fin.bgP = f.temporal ? nullptr : w.bgP;
+  fin.bs_p = w.bs_p; fin.per_sample_p = f.per_sample_p;
+  fin.bs_ph = f.temporal ? w.bs_ph : nullptr; fin.per_sample_ph = f.per_sample_ph;
+  fin.bs_sh = f.main_t ? w.bs_sh : nullptr; fin.per_sample_sh = f.per_sample_sh;
+  fin.bs_d = f.stu_deferred ? w.bs_d : nullptr;
+  fin.K = a->K; fin.per_sample = f.per_sample; fin.per_sample_t = f.per_sample_t; fin.B = B; fin.H = a->H; fin.W = a->W;
   fin.w_main = a->w_main; fin.w_distil = a->w_distil;
   fin.ps = w.ps; fin.gT0 = w.gT[0]; fin.gT1 = w.gT[1]; fin.stats = w.sm_stats; fin.losses = a->losses; fin.coefs = w.coefs;
   fin.loss_total = a->loss_total; fin.ticket = w.ticket;
   fin.noise_counter = (a->flags & MAL_STEP_NOISE_PHILOX) ? (unsigned long long*)a->noise_counter : nullptr;
-  hipLaunchKernelGGL(step_final_kernel, dim3(temporal ? 2 * B : 3 * B), dim3(256), 0, st, fin);
+  hipLaunchKernelGGL(step_final_kernel, dim3(f.temporal ? 2 * B : 3 * B), dim3(256), 0, st, fin);
   return launch_status();
+}
+static int step_fwd_body(const mal_step_args* a, const StepWs& w, hipStream_t st, StepFwd& f) {
+  int rc = fwd_front(a, w, st, f);
+  if (!rc) rc = fwd_sweeps(a, w, st, f);
+  if (!rc) rc = fwd_join(a, w, st, f);
+  if (!rc) rc = fwd_student(a, w, st, f);
+  if (!rc) rc = fwd_reduce(a, w, st, f);
+  return rc;
+}
+extern "C" int mal_loss_step_fwd(const mal_step_args* a) {
+  int rc = step_check(a);
+  if (rc) return rc;
+  const StepWs w = step_ws(a);
+  StepFwd f = {};
+  f.no_ens = a->flags & MAL_STEP_NO_ENS; f.temporal = a->flags & MAL_STEP_TEMPORAL; f.main_t = a->flags & MAL_STEP_MAIN_TEMPORAL;
+  f.hinted = f.temporal || f.main_t;
+  f.mono_reproj = a->mono_reproj ? a->mono_reproj : w.mono_reproj;
+  f.ens_reproj = f.no_ens ? nullptr : (a->ens_reproj ? a->ens_reproj : w.ens_reproj);
+  f.per_sample_p = f.per_sample = 1;
+  rc = step_fwd_body(a, w, (hipStream_t)a->stream, f);
+  // the one exit: a hinted step that fails joins what mal_loss_step_warp (or this call) forked (a no-op once fwd_join has run);
+  // a step without the hint forked nothing and must not create the side stream
+  if (rc && f.hinted) (void)join_side((hipStream_t)a->stream);
+  return rc;
 }
 
 // Measurement hook (bench.py): `launches` back-to-back launches of the teacher's pass exactly as mal_loss_step_fwd enqueues
@@ -1065,8 +1071,7 @@ extern "C" int mal_loss_step_teacher_replay(const mal_step_args* a, int launches
   int rc = step_check(a);
   if (rc) return rc;
   if ((a->flags & (MAL_STEP_TEMPORAL | MAL_STEP_MAIN_TEMPORAL)) || launches <= 0 || launches > 4096) return MAL_EINVAL;
-  StepWs w = carve_step(a->ws, a->B, a->H, a->W);
-  use_texel_inputs(a, w);
+  const StepWs w = step_ws(a);
   float* mono_reproj = a->mono_reproj ? a->mono_reproj : w.mono_reproj;
   for (int i = 0; i < launches; ++i) {
     rc = launch_teacher(a, w, mono_reproj, (hipStream_t)a->stream);
@@ -1075,97 +1080,84 @@ extern "C" int mal_loss_step_teacher_replay(const mal_step_args* a, int launches
   return MAL_OK;
 }
 
-extern "C" int mal_loss_step_bwd(const mal_step_args* a) {
-  int rc = step_check(a);
-  if (rc) return rc;
+// the teacher's gradient sweep of a --temporal step, with the decisions of the four-way min taken from _fwd and the gradient that
+// reaches the warped images through syn added before the chain rule through the warp; *teacher_done: it wrote d total /
+// d disp_teacher itself
+static int launch_teacher_temporal(const mal_step_args* a, const StepWs& w, SideStream* tail, hipStream_t st, int* per_sample_t,
+                                   bool* teacher_done) {
+  if (!a->g_warp_m1 || !a->g_warp_p1) return MAL_EINVAL;
+  MarchParams p = teacher_params(a, w, nullptr);
+  p.g_reproj = w.G_r_t; p.block_sums = w.bs_t;
+  p.ident = w.ident;  // unused by the TEMPORAL instantiation (the launch checks the flag combination only)
+  p.forced_w = w.w_t; p.forced_arg = w.arg_t; p.g_color[0] = a->g_warp_m1; p.g_color[1] = a->g_warp_p1;
+  if (g_temporal_spec) {
+    // mal_loss_step_warp left the gradient as it is without the synthesised candidates: only the tasks near the region
+    // map are redone (all of them without a map); the assembly finishes the teacher's gradient as in the plain step.
+    // The sums of the redone tasks are not the step's (those are the pass's in front + the fused sweep's differences)
+    p.region = a->syn_region; p.block_sums = w.bs_e;
+  } else if (tail) {
+    // beside the reduction: the loss scalars may not exist yet -- the sweep leaves the unnormalised map (the assembly finishes
+    // it, as in the step without the hint) and its sums go to a scratch of their own (the reduction reads bs_t meanwhile)
+    p.block_sums = w.bs_e;
+  } else {
+    // the loss scalars exist already: the sweep writes d total / d disp_teacher itself (the assembly does the student's)
+    p.fin_gn = w.gn_t; p.fin_coefs = w.coefs; p.fin_stats = w.sm_stats; p.fin_g_total = a->g_total; p.fin_out = a->g_disp_teacher;
+    *teacher_done = a->g_disp_teacher != nullptr;
+  }
+  p.bnd = halo_bnd(w.bnd_t);
+  p.dbg = a->dec_teacher;
+  const int rc = march_launch(p, MAL_F_AUTOMASK | MAL_F_GRAD | MAL_F_POSE_GRAD | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
+  *per_sample_t = p.strips * p.segs;
+  return rc;
+}
+// tail (option "tail_overlap", nullable): the sweeps run on the side stream, behind the producers' backwards
+static int step_bwd_body(const mal_step_args* a, const StepWs& w, SideStream* tail, hipStream_t st) {
   const int B = a->B, H = a->H, W = a->W, HW = H * W;
-  StepWs w = carve_step(a->ws, B, H, W);
-  use_texel_inputs(a, w);
-  hipStream_t st = (hipStream_t)a->stream;
   int per_sample_t = 0;
   bool teacher_done = false;
-  SideStream* tail = nullptr;  // option "tail_overlap": the sweeps below run on the side stream, behind the producers' backwards
-  if (tail_applies(a)) {
-    SideStream* ss = side_stream(st);
-    if (ss && ss->tail_pending) tail = ss;
-  }
-  rc = step_geom_check(a->ws, B, H, W);  // the boundary rows, partials and task counts of _fwd need the decomposition it used
-  if (rc) { if (tail) (void)join_tail(tail, st); return rc; }
-  if (a->flags & MAL_STEP_TEMPORAL) {
-    // the teacher's gradient sweep, with the decisions of the four-way min taken from _fwd and the gradient that
-    // reaches the warped images through syn added before the chain rule through the warp
-    if (!a->g_warp_m1 || !a->g_warp_p1) { if (tail) (void)join_tail(tail, st); return MAL_EINVAL; }
-    MarchParams p = teacher_params(a, w, nullptr);
-    p.g_reproj = w.G_r_t; p.block_sums = w.bs_t;
-    p.ident = w.ident;  // unused by the TEMPORAL instantiation (the launch checks the flag combination only)
-    p.forced_w = w.w_t; p.forced_arg = w.arg_t; p.g_color[0] = a->g_warp_m1; p.g_color[1] = a->g_warp_p1;
-    if (g_temporal_spec) {
-      // mal_loss_step_warp left the gradient as it is without the synthesised candidates: only the tasks near the region
-      // map are redone (all of them without a map); the assembly finishes the teacher's gradient as in the plain step.
-      // The sums of the redone tasks are not the step's (those are the pass's in front + the fused sweep's differences)
-      p.region = a->syn_region; p.block_sums = w.bs_e;
-    } else if (tail) {
-      // beside the reduction: the loss scalars may not exist yet -- the sweep leaves the unnormalised map (the assembly finishes
-      // it, as in the step without the hint) and its sums go to a scratch of their own (the reduction reads bs_t meanwhile)
-      p.block_sums = w.bs_e;
-    } else {
-      // the loss scalars exist already: the sweep writes d total / d disp_teacher itself (the assembly does the student's)
-      p.fin_gn = w.gn_t; p.fin_coefs = w.coefs; p.fin_stats = w.sm_stats; p.fin_g_total = a->g_total; p.fin_out = a->g_disp_teacher;
-      teacher_done = a->g_disp_teacher != nullptr;
-    }
-    p.bnd = g_march_halo1 ? w.bnd_t : nullptr;
-    p.dbg = a->dec_teacher;
-    rc = march_launch(p, MAL_F_AUTOMASK | MAL_F_GRAD | MAL_F_POSE_GRAD | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, tail ? tail->s : st);
-    if (tail && rc) (void)join_tail(tail, st);  // (nothing may be left outside the caller's stream)
-    if (rc) return rc;
-    per_sample_t = p.strips * p.segs;
-  }
-  if (a->flags & MAL_STEP_MAIN_TEMPORAL) {
-    if (!a->g_warp_s_m1 || !a->g_warp_s_p1) { if (tail) (void)join_tail(tail, st); return MAL_EINVAL; }
-    rc = launch_student_temporal(a, w, tail ? tail->s : st);
-    if (tail && rc) (void)join_tail(tail, st);
-    if (rc) return rc;
-  }
+  int rc = step_geom_check(a->ws, B, H, W);  // the boundary rows, partials and task counts of _fwd need the decomposition it used
+  if (!rc && (a->flags & MAL_STEP_TEMPORAL)) rc = launch_teacher_temporal(a, w, tail, tail ? tail->s : st, &per_sample_t, &teacher_done);
+  if (!rc && (a->flags & MAL_STEP_MAIN_TEMPORAL))
+    rc = (!a->g_warp_s_m1 || !a->g_warp_s_p1) ? MAL_EINVAL : launch_student_temporal(a, w, tail ? tail->s : st);
+  if (rc) return rc;
   size_t g = (size_t)B * H;  // a workgroup per image row
   if (g > 4096) g = 4096;
   if (g < (size_t)B) g = (size_t)B;
   int segs = 0, rows = 0;
   march_geometry(B, H, W, MAL_F_GRAD, nullptr, &segs, &rows);  // the decomposition the gradient passes of this step used
-  PoseParams pp = {};
-  pp.B = B; pp.F = 2;
-  pp.axisangle[0] = a->axisangle_m1; pp.axisangle[1] = a->axisangle_p1;
-  pp.translation[0] = a->translation_m1; pp.translation[1] = a->translation_p1;
-  pp.invert[0] = 1; pp.invert[1] = 0;
-  pp.gT[0] = w.gTs[0]; pp.gT[1] = w.gTs[1];
-  pp.g_axisangle[0] = a->g_axisangle_m1; pp.g_axisangle[1] = a->g_axisangle_p1;
-  pp.g_translation[0] = a->g_translation_m1; pp.g_translation[1] = a->g_translation_p1;
   StepAssemble as = {};
+  const PoseParams pp = step_pose_bwd(a, w.gTs, &as.pose_bwd);
   as.G_r_t = w.G_r_t; as.G_r_s = w.G_r_s; as.G_cd = w.G_c; as.gn_t = w.gn_t; as.gn_s = w.gn_s;
   as.coefs = w.coefs; as.stats = w.sm_stats; as.g_total = a->g_total; as.B = B; as.HW = HW; as.W = W;
   as.gT0 = w.gT[0]; as.gT1 = w.gT[1]; as.gTs0 = w.gTs[0]; as.gTs1 = w.gTs[1];
   as.g_disp_t = teacher_done ? nullptr : a->g_disp_teacher; as.g_disp_s = a->g_disp_student;
-  as.pose_bwd = (a->g_axisangle_m1 || a->g_translation_m1 || a->g_axisangle_p1 || a->g_translation_p1) ? 1 : 0;
   as.bgP = per_sample_t ? w.bgP : nullptr; as.K = a->K; as.per_sample = per_sample_t;
-  as.bnd_t = g_march_halo1 ? w.bnd_t : nullptr; as.bnd_s = g_march_halo1 ? w.bnd_s : nullptr; as.rows = rows; as.segs = segs;
+  as.bnd_t = halo_bnd(w.bnd_t); as.bnd_s = halo_bnd(w.bnd_s); as.rows = rows; as.segs = segs;
   as.fix_t = teacher_done ? a->g_disp_teacher : nullptr;
   as.G_e = a->ens_disp ? w.G_e : nullptr; as.g_ens = a->ens_disp ? a->g_ens_disp : nullptr;
   as.G_dual = (a->flags & MAL_STEP_DUAL_DISTIL) ? w.G_e : nullptr;
-  auto assemble = [&](int parts, hipStream_t on) {
+  auto assemble = [&](int parts) {
     as.parts = parts;
-    hipLaunchKernelGGL(step_assemble_kernel, dim3((unsigned)g), dim3(256), 0, on, as, pp);
+    hipLaunchKernelGGL(step_assemble_kernel, dim3((unsigned)g), dim3(256), 0, st, as, pp);
     return launch_status();
   };
-  if (tail) {
-    // the student's half needs nothing of the side stream's chain (unless its own sweep runs there: --main_temporal; and
-    // --dual_distil adds a term of the epilogue to the TEACHER's map only): it goes out now, beside the teacher's sweep
-    const bool split = !(a->flags & MAL_STEP_MAIN_TEMPORAL) && a->g_disp_student != nullptr;
-    if (split) {
-      rc = assemble(2, st);
-      if (rc) { (void)join_tail(tail, st); return rc; }
-    }
-    rc = join_tail(tail, st);  // the sweep's results (and the producer's backward in front of it) come back to the caller's stream
-    if (rc) return rc;
-    return assemble(split ? 5 : 7, st);
-  }
-  return assemble(7, st);
+  if (!tail) return assemble(7);
+  // the student's half needs nothing of the side stream's chain (unless its own sweep runs there: --main_temporal; and
+  // --dual_distil adds a term of the epilogue to the TEACHER's map only): it goes out now, beside the teacher's sweep
+  const bool split = !(a->flags & MAL_STEP_MAIN_TEMPORAL) && a->g_disp_student != nullptr;
+  if (split) rc = assemble(2);
+  if (!rc) rc = join_tail(tail, st);  // the sweep's results (and the producer's backward in front of it) come back to the caller's stream
+  if (!rc) rc = assemble(split ? 5 : 7);
+  return rc;
+}
+extern "C" int mal_loss_step_bwd(const mal_step_args* a) {
+  int rc = step_check(a);
+  if (rc) return rc;
+  const StepWs w = step_ws(a);
+  hipStream_t st = (hipStream_t)a->stream;
+  SideStream* ss = tail_applies(a) ? side_stream(st) : nullptr;
+  SideStream* tail = ss && ss->tail_pending ? ss : nullptr;
+  rc = step_bwd_body(a, w, tail, st);
+  if (rc && tail) (void)join_tail(tail, st);  // the one exit: nothing may be left outside the caller's stream (a no-op once joined)
+  return rc;
 }

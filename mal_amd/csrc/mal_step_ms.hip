@@ -56,7 +56,7 @@ static MsWs carve_ms(void* base, int B, int H, int W, int sclm) {
   size_t o = 0;
   const int S = sclm + 1;
   const size_t HW = (size_t)H * W, map = B * HW * sizeof(float), nb = ws_blocks(B, H, W);
-  auto take = [&](size_t bytes) { char* r = p + o; o += align256(bytes); return r; };
+  auto take = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align256(bytes); return r; };  // (null base: sizing only)
   for (int i = 0; i < 3; ++i) w.packed[i] = (float*)take(B * HW * kTexel * sizeof(float));
   for (int f = 0; f < 2; ++f) { w.T[f] = (float*)take(B * 16 * 4); w.gTs[f] = (float*)take(B * 16 * 4); }
   w.cam = (float*)take((size_t)B * kCamFloats * 4);
@@ -408,13 +408,23 @@ static const float* ms_noise(const mal_ms_args* a, const MsWs& w, int s) {
   return (a->flags & MAL_STEP_NOISE_PHILOX) ? w.noise[s] : a->noise[s];
 }
 static MarchParams ms_teacher_params(const mal_ms_args* a, const MsWs& w, int s) {
-  MarchParams p = march_params(a->B, a->H, a->W, a->min_depth, a->max_depth, 1e-7f, 0);
-  p.disp = s ? w.up[0][s] : a->disp_teacher[0]; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
-  p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+  MarchParams p = step_march_params(a, 0, w.T[0], w.T[1], w.packed, w.cam);
+  p.disp = s ? w.up[0][s] : a->disp_teacher[0];
   p.block_sums = w.bs[0][s]; p.block_gP = w.bgP[s];
-  p.cam = w.cam; p.cam_ready = 1;
   p.no_ssim = (a->flags & MAL_STEP_NO_SSIM) ? 1 : 0;
   return p;
+}
+// the fused sweep of scale s over the teacher's synthesised pair (temporal hint)
+static FusedMoreArgs ms_sweep(const mal_ms_args* a, const MsWs& w, int s) {
+  const bool sparse = (a->syn_sparse >> s) & 1;
+  FusedMoreArgs x = {};
+  x.target = w.packed[0]; x.cand0 = a->syn_m1[s]; x.cand1 = a->syn_p1[s]; x.idx0 = 2; x.ident = w.ident; x.noise = ms_noise(a, w, s);
+  x.prev_min = w.rp_warp[s]; x.prev_arg = w.arg_warp[s]; x.min_reproj = w.rp4[s]; x.argmin = w.arg_t[s]; x.weight_out = w.w_t[s];
+  x.block_sums = w.bs_ph[s]; x.g_cand0 = a->g_syn_m1[s]; x.g_cand1 = a->g_syn_p1[s]; x.region = a->syn_region[s];
+  x.g_region0 = a->g_syn_region_m1[s]; x.g_region1 = a->g_syn_region_p1[s];
+  x.orig0 = sparse ? a->warp_m1[s] : nullptr; x.orig1 = sparse ? a->warp_p1[s] : nullptr;
+  x.orig_stride = (size_t)a->warp_sample_stride;
+  return x;
 }
 static void ms_fold_launch(const MsWs& w, int B, int H, int W, int S, bool teachers, bool students, hipStream_t st) {
   MsFold f = {};
@@ -427,20 +437,14 @@ static void ms_fold_launch(const MsWs& w, int B, int H, int W, int S, bool teach
   if (n) hipLaunchKernelGGL(ms_fold_kernel, dim3((unsigned)(B * segs * 2), (unsigned)n), dim3(256), 0, st, f);
 }
 
-// everything that does not wait for a temporal-hint producer
-static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool temporal, int* per_sample_sm /*[S]*/, int* forked) {
-  *forked = 0;
+// everything that does not wait for a temporal-hint producer; *forked: the side stream was forked off `st` (ms_front closes it)
+static int ms_front_launches(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool temporal, int* per_sample_sm /*[S]*/,
+                             bool* forked) {
   const int B = a->B, H = a->H, W = a->W, S = a->sclm + 1;
   int rc;
   // 1. first sweep: identity term (no noise: every scale adds its own), texel packing, poses, camera block
   {
-    StepPoses sp = {};
-    sp.pose.B = B; sp.pose.F = 2;
-    sp.pose.axisangle[0] = a->axisangle_m1; sp.pose.axisangle[1] = a->axisangle_p1;
-    sp.pose.translation[0] = a->translation_m1; sp.pose.translation[1] = a->translation_p1;
-    sp.pose.invert[0] = 1; sp.pose.invert[1] = 0;
-    sp.pose.T[0] = w.T[0]; sp.pose.T[1] = w.T[1];
-    sp.K = a->K; sp.invK = a->inv_K; sp.cam = w.cam; sp.ticket = w.ticket;
+    const StepPoses sp = step_poses(a, w.T, w.cam, w.ticket);
     // 2. every scale's disparity at full resolution (trainer.py:1094-1096) and the per-scale tie-break noise maps: neither
     // reads what the sweep writes -- they ride on its launch as extra workgroups (four pixels per thread: W % 4 == 0 and
     // 16-byte aligned maps; launches of their own otherwise)
@@ -463,9 +467,11 @@ static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool te
       x.noise_blocks = (int)(((size_t)B * ((H + 3) / 4) * W + 63) / 64);
       x.up_blocks = (int)(((size_t)B * H * (W / 4) + 63) / 64);
     }
-    rc = pack_identity_launch(a->color0, a->color_m1, a->color_p1, B, H, W, w.packed[1], w.packed[2], w.packed[0], w.ident, st,
-                              &sp, nullptr, nullptr, nullptr, false, (a->flags & MAL_STEP_NO_SSIM) ? 1 : 0, nullptr,
-                              fold ? &x : nullptr);
+    PackIdentityArgs pk = {};
+    pk.target = a->color0; pk.src[0] = a->color_m1; pk.src[1] = a->color_p1;
+    pk.packed[0] = w.packed[1]; pk.packed[1] = w.packed[2]; pk.packed_target = w.packed[0]; pk.ident = w.ident;
+    pk.poses = &sp; pk.variant = (a->flags & MAL_STEP_NO_SSIM) ? 1 : 0; pk.ms = fold ? &x : nullptr;
+    rc = pack_identity_launch(pk, B, H, W, st);
     if (rc) return rc;
     if (!fold) {
       if (philox) {
@@ -496,16 +502,15 @@ static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool te
       p.color_out[0] = a->warp_m1[s]; p.color_out[1] = a->warp_p1[s]; p.color_out_stride = a->warp_sample_stride;
       return march_launch(p, MAL_F_AUTOMASK | packed, st);
     }
-    p.g_reproj = w.G_r[0][s]; p.bnd = g_march_halo1 ? w.bnd[0][s] : nullptr;
+    p.g_reproj = w.G_r[0][s]; p.bnd = halo_bnd(w.bnd[0][s]);
     p.dbg = a->dec_teacher[s];
     return march_launch(p, MAL_F_AUTOMASK | MAL_F_GRAD | MAL_F_POSE_GRAD | packed, st);
   };
   auto student = [&](int s, hipStream_t q) -> int {
     // mask = consistency (x matching, formed at scale 0 from the teacher's scale-0 depth, trainer.py:592-593)
     // x (1 - augmentation); consistency term against the teacher's depth of the same scale (:1330-1336)
-    MarchParams p = march_params(B, H, W, a->min_depth, a->max_depth, 1e-7f, 0);
-    p.disp = s ? w.up[1][s] : a->disp_student[0]; p.K = a->K; p.invK = a->inv_K; p.T[0] = w.T[0]; p.T[1] = w.T[1];
-    p.src[0] = w.packed[1]; p.src[1] = w.packed[2]; p.target = w.packed[0];
+    MarchParams p = step_march_params(a, 0, w.T[0], w.T[1], w.packed, w.cam);
+    p.disp = s ? w.up[1][s] : a->disp_student[0];
     if (!(a->flags & MAL_STEP_NO_AUG)) { p.sample_scale = a->augmentation_keep; p.sample_scale_is_mask = (a->flags & MAL_STEP_AUG_MASK) ? 1 : 0; }
     p.mono_disp = s ? w.up[0][s] : a->disp_teacher[0];
     if (a->flags & MAL_STEP_NO_MOTION_MASK) {
@@ -517,7 +522,7 @@ static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool te
       p.ext_mask = a->lowest_cost ? (a->consistency_mask_out ? a->consistency_mask_out : w.cmask) : a->consistency_mask;
     }
     p.mono_reproj = w.ident;  // the distillation selection is not part of this loss: any map serves, its term has weight 0
-    p.g_reproj = w.G_r[1][s]; p.g_cons = w.G_c[s]; p.g_distil = nullptr; p.bnd = g_march_halo1 ? w.bnd[1][s] : nullptr;
+    p.g_reproj = w.G_r[1][s]; p.g_cons = w.G_c[s]; p.g_distil = nullptr; p.bnd = halo_bnd(w.bnd[1][s]);
     p.merge_cons = merge_cons; p.merge_distil = 0.f;
     if (a->flags & MAL_STEP_ENSEMBLE) {
       // --ensemble (trainer.py:1346-1351): |(mono + multi)/2 - multi| * mask IS the distillation term with the ensemble winning
@@ -525,7 +530,6 @@ static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool te
       p.ens_reproj = w.neg_inf; p.merge_distil = merge_cons;
     }
     p.block_sums = w.bs[1][s]; p.block_gP = w.bgP[s];
-    p.cam = w.cam; p.cam_ready = 1;
     p.no_ssim = (a->flags & MAL_STEP_NO_SSIM) ? 1 : 0;
     p.dbg = a->dec_student[s];
     return march_launch(p, MAL_F_GRAD | MAL_F_EPILOGUE | packed, q);
@@ -547,79 +551,60 @@ static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool te
       if (rc) return rc;
     }
     hipStream_t side = side_begin(st);
-    if (side) { st2 = side; *forked = 1; }
+    if (side) { st2 = side; *forked = true; }
     for (int s = 0; s < S && !rc; ++s) rc = student(s, st2);
-    if (rc) { if (*forked) (void)side_end(st); return rc; }
+    if (rc) return rc;
   }
   if (g_march_halo1) {  // one-row halo of the gradient passes: each boundary row's missing window row, in ONE launch
     ms_fold_launch(w, B, H, W, S, !temporal, true, st2);
     rc = launch_status();
-    if (rc) { if (*forked) (void)side_end(st); return rc; }
+    if (rc) return rc;
   }
-  {  // smoothness of both disparity maps at every scale's own size against the target at that size (:1469-1471): ONE launch
-    const float *sd[2 * kMsS], *si[2 * kMsS];
-    float* sg[2 * kMsS];
-    double* sp[2 * kMsS];
-    int sh[2 * kMsS], sw[2 * kMsS], per[2 * kMsS];
-    for (int s = 0; s < S; ++s)
-      for (int n = 0; n < 2; ++n) {
-        const int k = 2 * s + n;
-        sd[k] = n ? a->disp_student[s] : a->disp_teacher[s];
-        si[k] = (s == 0 && !a->color0_s[0]) ? a->color0 : a->color0_s[s];
-        sg[k] = w.gn[n][s]; sp[k] = w.sm[n][s]; sh[k] = H >> s; sw[k] = W >> s;
-      }
-    rc = smooth_march_sweep_batch(2 * S, sd, si, B, sh, sw, sg, sp, st2, per);
-    if (rc) { if (*forked) (void)side_end(st); return rc; }
-    for (int s = 0; s < S; ++s) per_sample_sm[s] = per[2 * s];
-  }
-  if (*forked) return side_end(st);
-  return MAL_OK;
+  // smoothness of both disparity maps at every scale's own size against the target at that size (:1469-1471): ONE launch
+  SmoothMapArgs maps[2 * kMsS];
+  int per[2 * kMsS] = {};
+  for (int s = 0; s < S; ++s)
+    for (int n = 0; n < 2; ++n)
+      maps[2 * s + n] = {n ? a->disp_student[s] : a->disp_teacher[s], (s == 0 && !a->color0_s[0]) ? a->color0 : a->color0_s[s],
+                         H >> s, W >> s, w.gn[n][s], w.sm[n][s]};
+  rc = smooth_march_sweep_batch(2 * S, maps, B, st2, per);
+  for (int s = 0; s < S; ++s) per_sample_sm[s] = per[2 * s];
+  return rc;
 }
-
-// tasks per sample of the smoothness sweep of scale s (the sweep ran in an earlier call: mal_loss_multiscale_warp)
-static int ms_smooth_tasks(int H, int W, int s) { return smooth_march_batch_tasks(H >> s, W >> s); }
+// ... and the one place that closes its fork: whatever went onto the side stream, on every exit, is behind the join event
+// that mal_loss_multiscale_fwd (or _abort, or the next step's _warp) waits for
+static int ms_front(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool temporal, int* per_sample_sm /*[S]*/) {
+  bool forked = false;
+  int rc = ms_front_launches(a, w, st, temporal, per_sample_sm, &forked);
+  if (forked) { const int e = side_end(st); if (!rc) rc = e; }
+  return rc;
+}
 
 // the fused sweeps of the temporal hint (one per scale) and the reduction
 static int ms_back(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool temporal, const int* per_sample_sm) {
   const int B = a->B, H = a->H, W = a->W, S = a->sclm + 1;
   MsFinal fin = {};
-  int strips = 0, segs = 0;
-  march_geometry(B, H, W, MAL_F_GRAD, &strips, &segs, nullptr);
-  fin.per_sample = strips * segs; fin.per_sample_t = fin.per_sample;
+  fin.per_sample = march_tasks_per_sample(B, H, W, MAL_F_GRAD);
+  fin.per_sample_t = temporal ? march_tasks_per_sample(B, H, W, 0) : fin.per_sample;
   if (temporal) {
-    march_geometry(B, H, W, 0, &strips, &segs, nullptr);
-    fin.per_sample_t = strips * segs;
     // every scale's sweep in ONE launch when all of them have a region map (same decomposition): each is a few short tasks
     bool batch = g_ms_fold && S > 1;
     for (int s = 0; s < S; ++s) batch = batch && a->syn_region[s] != nullptr;
     FusedMoreArgs fa[kMsS] = {};
     for (int s = 0; s < S; ++s) {
-      if (!a->syn_m1[s] || !a->syn_p1[s] || !a->g_syn_m1[s] || !a->g_syn_p1[s]) { (void)side_wait(st, false); return MAL_EINVAL; }
+      if (!a->syn_m1[s] || !a->syn_p1[s] || !a->g_syn_m1[s] || !a->g_syn_p1[s]) return MAL_EINVAL;
       const bool sparse = (a->syn_sparse >> s) & 1;
-      if (sparse && (!a->syn_region[s] || !a->warp_m1[s] || !a->warp_p1[s])) { (void)side_wait(st, false); return MAL_EINVAL; }
-      if (batch) {
-        FusedMoreArgs& x = fa[s];
-        x.target = w.packed[0]; x.cand0 = a->syn_m1[s]; x.cand1 = a->syn_p1[s]; x.idx0 = 2; x.ident = w.ident; x.noise = ms_noise(a, w, s);
-        x.prev_min = w.rp_warp[s]; x.prev_arg = w.arg_warp[s]; x.min_reproj = w.rp4[s]; x.argmin = w.arg_t[s]; x.weight_out = w.w_t[s];
-        x.block_sums = w.bs_ph[s]; x.g_cand0 = a->g_syn_m1[s]; x.g_cand1 = a->g_syn_p1[s]; x.region = a->syn_region[s];
-        x.g_region0 = a->g_syn_region_m1[s]; x.g_region1 = a->g_syn_region_p1[s];
-        x.orig0 = sparse ? a->warp_m1[s] : nullptr; x.orig1 = sparse ? a->warp_p1[s] : nullptr;
-        x.orig_stride = (size_t)a->warp_sample_stride; x.weight_given = 0;
-        fin.bs_ph[s] = w.bs_ph[s];
-        continue;
-      }
-      int rc = photo_march_fused_more(w.packed[0], a->syn_m1[s], a->syn_p1[s], 2, w.ident, ms_noise(a, w, s), w.rp_warp[s],
-                                      w.arg_warp[s], B, H, W, w.rp4[s], w.arg_t[s], w.w_t[s], w.bs_ph[s], a->g_syn_m1[s],
-                                      a->g_syn_p1[s], &fin.per_sample_ph[s], st, a->syn_region[s], a->g_syn_region_m1[s],
-                                      a->g_syn_region_p1[s], nullptr, nullptr, sparse ? a->warp_m1[s] : nullptr,
-                                      sparse ? a->warp_p1[s] : nullptr, (size_t)a->warp_sample_stride, 1, 0);
-      if (rc) { (void)side_wait(st, false); return rc; }
+      if (sparse && (!a->syn_region[s] || !a->warp_m1[s] || !a->warp_p1[s])) return MAL_EINVAL;
+      fa[s] = ms_sweep(a, w, s);
       fin.bs_ph[s] = w.bs_ph[s];
+      if (batch) continue;
+      const int rc = photo_march_fused_more(fa[s], B, H, W, &fin.per_sample_ph[s], st);
+      if (rc) return rc;
     }
     if (batch) {
       int per = 0;
       const int rc = photo_march_fused_more_n(S, fa, B, H, W, &per, st);
-      if (rc) { (void)side_wait(st, false); return rc; }
+      if (rc) return rc;
       for (int s = 0; s < S; ++s) fin.per_sample_ph[s] = per;
     }
     // the students' passes and the smoothness sweeps ran on the side stream beside the producers (mal_loss_multiscale_warp)
@@ -646,11 +631,11 @@ extern "C" int mal_loss_multiscale_warp(const mal_ms_args* a) {
   for (int s = 0; s <= a->sclm; ++s)
     if (!a->warp_m1[s] || !a->warp_p1[s]) return MAL_EINVAL;
   MsWs w = carve_ms(a->ws, a->B, a->H, a->W, a->sclm);
-  int per_sm[kMsS], forked = 0;
+  int per_sm[kMsS];
   rc = side_wait((hipStream_t)a->stream, false);  // a previous step that was abandoned after its fork
   if (rc) return rc;
   step_geom_record(a->ws, a->B, a->H, a->W);
-  return ms_front(a, w, (hipStream_t)a->stream, true, per_sm, &forked);
+  return ms_front(a, w, (hipStream_t)a->stream, true, per_sm);  // (closes its fork on every exit)
 }
 
 // A MAL_STEP_TEMPORAL step that called mal_loss_multiscale_warp but will not call _fwd (a producer raised): joins the side stream
@@ -659,23 +644,30 @@ extern "C" int mal_loss_multiscale_abort(const mal_ms_args* a) {
   return side_wait((hipStream_t)a->stream, false);
 }
 
+static int ms_fwd_body(const mal_ms_args* a, const MsWs& w, hipStream_t st, bool temporal) {
+  int per_sm[kMsS] = {};
+  if (!temporal) {
+    step_geom_record(a->ws, a->B, a->H, a->W);
+    const int rc = ms_front(a, w, st, false, per_sm);
+    if (rc) return rc;
+  } else {
+    if (step_geom_check(a->ws, a->B, a->H, a->W)) return MAL_ESTALE;  // options changed after _warp
+    // tasks per sample of each scale's smoothness sweep (it ran in mal_loss_multiscale_warp)
+    for (int s = 0; s <= a->sclm; ++s) per_sm[s] = smooth_march_batch_tasks(a->H >> s, a->W >> s);
+  }
+  return ms_back(a, w, st, temporal, per_sm);
+}
 extern "C" int mal_loss_multiscale_fwd(const mal_ms_args* a) {
   int rc = ms_check(a);
   if (rc) return rc;
   MsWs w = carve_ms(a->ws, a->B, a->H, a->W, a->sclm);
   hipStream_t st = (hipStream_t)a->stream;
   const bool temporal = (a->flags & MAL_STEP_TEMPORAL) != 0;
-  int per_sm[kMsS] = {};
-  if (!temporal) {
-    step_geom_record(a->ws, a->B, a->H, a->W);
-    int forked = 0;
-    rc = ms_front(a, w, st, false, per_sm, &forked);
-    if (rc) return rc;
-  } else {
-    if (step_geom_check(a->ws, a->B, a->H, a->W)) { (void)side_wait(st, false); return MAL_ESTALE; }  // options changed after _warp
-    for (int s = 0; s <= a->sclm; ++s) per_sm[s] = ms_smooth_tasks(a->H, a->W, s);
-  }
-  return ms_back(a, w, st, temporal, per_sm);
+  rc = ms_fwd_body(a, w, st, temporal);
+  // the one exit: a hinted step that fails joins what mal_loss_multiscale_warp forked (a no-op once ms_back has joined it); a step
+  // without the hint forked nothing and must not create the side stream
+  if (rc && temporal) (void)side_wait(st, false);
+  return rc;
 }
 
 extern "C" int mal_loss_multiscale_bwd(const mal_ms_args* a) {
@@ -694,7 +686,7 @@ extern "C" int mal_loss_multiscale_bwd(const mal_ms_args* a) {
       if (!a->g_warp_m1[s] || !a->g_warp_p1[s]) return MAL_EINVAL;
       MarchParams p = ms_teacher_params(a, w, s);
       p.ident = w.ident;  // unused by the TEMPORAL instantiation (the launch checks the flag combination only)
-      p.g_reproj = w.G_r[0][s]; p.bnd = g_march_halo1 ? w.bnd[0][s] : nullptr;
+      p.g_reproj = w.G_r[0][s]; p.bnd = halo_bnd(w.bnd[0][s]);
       p.forced_w = w.w_t[s]; p.forced_arg = w.arg_t[s]; p.g_color[0] = a->g_warp_m1[s]; p.g_color[1] = a->g_warp_p1[s];
       p.dbg = a->dec_teacher[s];
       rc = march_launch(p, MAL_F_AUTOMASK | MAL_F_GRAD | MAL_F_POSE_GRAD | MAL_F_SRC_PACKED | MAL_F_TGT_PACKED, st);
@@ -719,15 +711,8 @@ extern "C" int mal_loss_multiscale_bwd(const mal_ms_args* a) {
   }
   p.coefs = w.coefs; p.stats = w.stats; p.g_total = a->g_total; p.gT = w.gT; p.gTs0 = w.gTs[0]; p.gTs1 = w.gTs[1];
   p.B = B; p.H = H; p.W = W; p.S = S;
-  PoseParams pp = {};
-  pp.B = B; pp.F = 2;
-  pp.axisangle[0] = a->axisangle_m1; pp.axisangle[1] = a->axisangle_p1;
-  pp.translation[0] = a->translation_m1; pp.translation[1] = a->translation_p1;
-  pp.invert[0] = 1; pp.invert[1] = 0;
-  pp.gT[0] = w.gTs[0]; pp.gT[1] = w.gTs[1];
-  pp.g_axisangle[0] = a->g_axisangle_m1; pp.g_axisangle[1] = a->g_axisangle_p1;
-  pp.g_translation[0] = a->g_translation_m1; pp.g_translation[1] = a->g_translation_p1;
-  const int pose_bwd = (a->g_axisangle_m1 || a->g_translation_m1 || a->g_axisangle_p1 || a->g_translation_p1) ? 1 : 0;
+  int pose_bwd = 0;
+  const PoseParams pp = step_pose_bwd(a, w.gTs, &pose_bwd);
   // one unit of work per thread: B*H*W / 4 quads at scale 0 (B*H*W when W % 4 != 0), B*H*W / 2**s group members above;
   // a pass whose output is not wanted gets no workgroups (pass 0 keeps one: it carries the pose backward)
   bool vec0 = W % 4 == 0;

@@ -278,7 +278,7 @@ def test_a_raising_producer_leaves_the_library_usable():
         losses, _, _ = step.loss_step(opt, inputs, mono_outputs, outputs, w_list=[0.7, 0.3], noise=n0.to(dev), image_synthesis=producer)
         losses["loss"].backward()
         torch.cuda.synchronize()
-        return float(losses["loss"]), leaves["disp_teacher"].grad.cpu().numpy()
+        return float(losses["loss"].detach()), leaves["disp_teacher"].grad.cpu().numpy()
 
     class Boom(Exception):
         pass
@@ -292,6 +292,94 @@ def test_a_raising_producer_leaves_the_library_usable():
             run(raising)
     again = run(lambda i, o, s: False)
     assert again[0] == ref[0] and np.array_equal(again[1], ref[1])
+
+
+def _int_option(lib, name):
+    import ctypes
+    v = ctypes.c_int()
+    assert lib.mal_get_option(name.encode(), ctypes.byref(v)) == 0, name
+    return v.value
+
+
+@pytest.fixture
+def march_rows_restored():
+    """the library handle; option "march_rows" is put back whether the test passes or fails"""
+    from mal_amd import _lib
+    lib = _lib.load()
+    old = _int_option(lib, "march_rows")
+    try:
+        yield lib
+    finally:
+        lib.mal_set_option(b"march_rows", old)
+
+
+def _refused_forward_leaves_the_library_usable(lib, run):
+    """``run(producer) -> (loss, d loss / d disp_teacher)``: a producer that changes the task decomposition between the step's
+    first call and its forward makes the forward refuse (MAL_ESTALE) AFTER the first call forked work onto the library's side
+    stream; the refusing exit joins it, so the next step is bit-equal to one taken before"""
+    from mal_amd import _lib
+    old = _int_option(lib, "march_rows")
+
+    def stale(inputs_, outputs_, scale):
+        _lib.check(lib.mal_set_option(b"march_rows", 9), "march_rows")
+        return False
+
+    ref = run(lambda i, o, s: False)
+    with pytest.raises(_lib.MalError, match="decomposition"):
+        run(stale)
+    _lib.check(lib.mal_set_option(b"march_rows", old), "march_rows")
+    again = run(lambda i, o, s: False)
+    assert again[0] == ref[0] and np.array_equal(again[1], ref[1])
+
+
+def test_a_stale_forward_of_the_temporal_step_joins_its_fork(march_rows_restored):
+    """step.loss_step, opt.temporal: mal_loss_step_fwd's MAL_ESTALE exit (join_side)"""
+    from mal_amd import step, trainer
+    z = G.load("step_b2_32x64_temporal")
+    b = G.batch_from_golden(z)
+    B, _, H, W = b["color0"].shape
+    n0, _ = G.noises(z, (B, 1, H, W))
+    dev = torch.device(DEV)
+    opt = trainer.default_options(height=H, width=W, batch_size=B, temporal=True)
+
+    def run(producer):
+        inputs, mono_outputs, outputs, leaves = to_dicts(b, lambda a, t, inv: None, device=dev)
+        for f, s in ((-1, "m1"), (1, "p1")):
+            mono_outputs[("axisangle", 0, f)] = leaves["axisangle_" + s]
+            mono_outputs[("translation", 0, f)] = leaves["translation_" + s]
+        losses, _, _ = step.loss_step(opt, inputs, mono_outputs, outputs, w_list=[0.7, 0.3], noise=n0.to(dev), image_synthesis=producer)
+        losses["loss"].backward()
+        torch.cuda.synchronize()
+        return float(losses["loss"].detach()), leaves["disp_teacher"].grad.cpu().numpy()
+
+    _refused_forward_leaves_the_library_usable(march_rows_restored, run)
+
+
+def test_a_stale_forward_of_the_multiscale_step_joins_its_fork(march_rows_restored):
+    """step.loss_step_multiscale, sclm = 1 without --distil, opt.temporal: mal_loss_multiscale_fwd's MAL_ESTALE exit (side_wait)"""
+    from mal_amd import step, trainer
+    z = G.load("step_b2_32x64_temporal")
+    b = G.batch_from_golden(z)
+    B, _, H, W = b["color0"].shape
+    n0, n1 = G.noises(z, (B, 1, H, W))
+    dev = torch.device(DEV)
+    opt = trainer.default_options(height=H, width=W, batch_size=B, sclm=1, distil=False, temporal=True)
+
+    def run(producer):
+        inputs, mono_outputs, outputs, leaves = to_dicts(b, lambda a, t, inv: None, device=dev)
+        for f, s in ((-1, "m1"), (1, "p1")):
+            mono_outputs[("axisangle", 0, f)] = leaves["axisangle_" + s]
+            mono_outputs[("translation", 0, f)] = leaves["translation_" + s]
+        inputs[("color", 0, 1)] = torch.nn.functional.avg_pool2d(b["color0"], 2).to(dev)
+        for name, outs in (("disp_teacher", mono_outputs), ("disp_student", outputs)):
+            outs[("disp", 1)] = torch.nn.functional.avg_pool2d(b[name], 2).to(dev).clone().requires_grad_(True)
+        losses, _ = step.loss_step_multiscale(opt, inputs, mono_outputs, outputs, noises=[n0.to(dev), n1.to(dev)],
+                                              image_synthesis=producer)
+        losses["loss"].backward()
+        torch.cuda.synchronize()
+        return float(losses["loss"].detach()), leaves["disp_teacher"].grad.cpu().numpy()
+
+    _refused_forward_leaves_the_library_usable(march_rows_restored, run)
 
 
 @pytest.mark.parametrize("option,temporal", [("march3", False), ("temporal_spec", True)], ids=["march3", "temporal_spec"])
