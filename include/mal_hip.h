@@ -40,11 +40,16 @@ extern "C" {
 #define MAL_INSTANCES_MAX_QK 16384 /* mal_instances: queries x classes (Q*K) per image; Q=200, K=80 is 16000 */
 #define MAL_INSTANCES_MAX_K1 1025  /* mal_instances: logits per query (K+1) */
 #define MAL_INSTANCES_MAX_N 65535  /* mal_instances: images per call */
+#define MAL_MSDA_MAX_L 8    /* mal_msda_*: feature levels */
+#define MAL_MSDA_MAX_P 8    /* mal_msda_*: sampling points per head and level */
+#define MAL_MSDA_MAX_LP 32  /* mal_msda_*: L*P, the samples of one (query, head) */
+#define MAL_MSDA_MAX_D 64   /* mal_msda_*: channels per head */
 
 enum {
   MAL_OK = 0,
   MAL_EINVAL = -1,    /* bad argument (null pointer, non-positive size, F/n_cand out of range) */
-  MAL_ESHAPE = -2,    /* image smaller than 2x2 (reflection pad needs >= 2) or too large for int32 indexing */
+  MAL_ESHAPE = -2,    /* image smaller than 2x2 (reflection pad needs >= 2) or too large for int32 indexing; mal_msda_*: a
+                         size outside the bounds stated there */
   MAL_EWORKSPACE = -3,/* workspace too small: call mal_workspace_bytes */
   MAL_ELAUNCH = -4,   /* hipLaunchKernel / hipGetLastError failed */
   MAL_ENODEVICE = -5, /* no HIP device */
@@ -697,6 +702,42 @@ typedef struct mal_instances_args {
 size_t mal_instances_workspace_bytes(int N, int Q, int K, int h, int w, int H, int W, int topk); /* 0 for sizes mal_instances refuses */
 int mal_instances(const mal_instances_args* args);
 
+/* ---- N2, inside the segmenter: multi-scale deformable attention, FORWARD ONLY (the segmenter is frozen and runs under
+ * no_grad: manydepth/trainer.py:354, manydepth/dyn_utils.py:185-186).  The operator of Mask2Former's pixel decoder,
+ * mask2former/modeling/pixel_decoder/ops, whose upstream extension is CUDA-only.  All tensors fp32, contiguous, upstream's
+ * layouts.  Per (n, q, m):  out = sum_l sum_p w * bilinear(value_l, x * W_l - 0.5, y * H_l - 0.5), zero padding,
+ * align_corners=False: the arithmetic of ms_deformable_im2col_gpu_kernel (ops/src/cuda/ms_deform_im2col_cuda.cuh:242-304),
+ * the function ms_deform_attn_core_pytorch (ops/functions/ms_deform_attn_func.py:52-72) computes.  A sample counts only when
+ * y > -1 && x > -1 && y < H && x < W; every range test is made in float before any conversion to an index, so NaN and
+ * infinite locations contribute zero.
+ * mal_msda_fwd: sampling_locations (N,Lq,M,L,P,2) in (x, y) order and attention_weights (N,Lq,M,L,P) as given;
+ * reference_points and ref_dim are not read.
+ * mal_msda_fused_fwd: the module's default route (ops/modules/ms_deform_attn.py:102-112).  sampling_locations holds the
+ * raw OFFSETS (N,Lq,M,L,P,2) and attention_weights the raw LOGITS (N,Lq,M,L*P) of the two linear layers; the kernel takes
+ * the max-subtracted softmax over L*P and forms the locations from reference_points (N,Lq,L,ref_dim): ref_dim 2:
+ * ref + off / (W_l, H_l); ref_dim 4: ref[:2] + off / P * ref[2:] * 0.5 -- in torch's roundings (true divisions, no fma).
+ * spatial_shapes and level_start_index are DEVICE arrays read by the kernel (no readback: the call can be captured in a
+ * graph).  A level is used only if 1 <= H_l, W_l <= min(S, 2^24), level_start_index[l] >= 0 and level_start_index[l] +
+ * H_l W_l <= S; any other level contributes zero and reads nothing.
+ * Bounds: 1 <= L <= MAL_MSDA_MAX_L, 1 <= P <= MAL_MSDA_MAX_P, L*P <= MAL_MSDA_MAX_LP, 1 <= D <= MAL_MSDA_MAX_D, M >= 1,
+ * N, S, Lq >= 1, ref_dim 2 or 4 (fused), and value, out and sampling_locations below 2^31 elements each; anything else is
+ * MAL_ESHAPE.  A null args or a null required pointer is MAL_EINVAL (checked first, before any HIP call).  float4 loads and
+ * stores when D % 4 == 0 and value and out are 16-byte aligned, one channel per lane otherwise.  One launch on `stream`; no
+ * workspace, no allocation, no atomics, bit-reproducible. */
+typedef struct mal_msda_args {
+  const float* value;               /* (N,S,M,D) */
+  const int64_t* spatial_shapes;    /* device (L,2): H_l, W_l */
+  const int64_t* level_start_index; /* device (L) */
+  const float* sampling_locations;  /* (N,Lq,M,L,P,2); fused: the offsets */
+  const float* attention_weights;   /* (N,Lq,M,L,P);   fused: the logits */
+  const float* reference_points;    /* fused only: (N,Lq,L,ref_dim) */
+  int N, S, M, D, L, P, Lq, ref_dim;
+  float* out;                       /* (N,Lq,M*D) */
+  void* stream;
+} mal_msda_args;
+int mal_msda_fwd(const mal_msda_args* args);
+int mal_msda_fused_fwd(const mal_msda_args* args);
+
 /* ---- N3: ManyDepth's cost volume as MAL's student encoder builds it (forward only; upstream runs it under
  * no_grad): manydepth/networks/resnet_encoder.py:152-233 match_features + :296-312 of the encoder's forward.
  * current_feats (B,C,h,w) and lookup_feats (B,F,C,h,w) planar as the encoder produces them, C = 64 (with option
@@ -847,7 +888,7 @@ int mal_get_option(const char* name, int* value); /* the current value of an opt
  * thread, not on the arming one) and are taken with an atomic exchange: exactly one pass consumes an arm. */
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
 /* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
- * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args, 8 mal_instances_args;
+ * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args, 8 mal_instances_args, 9 mal_msda_args;
  * else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
 

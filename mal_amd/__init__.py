@@ -8,7 +8,7 @@ operators raise.
 """
 __version__ = "0.1.0"
 
-__all__ = ["HungarianMatcher", "InstanceSegmenter", "Instances", "instance_inference"]
+__all__ = ["HungarianMatcher", "InstanceSegmenter", "Instances", "instance_inference", "MSDeformAttn", "ms_deform_attn"]
 
 
 def __getattr__(name):
@@ -21,4 +21,8 @@ def __getattr__(name):
     if name in ("InstanceSegmenter", "Instances", "instance_inference"):
         from . import instances
         return getattr(instances, name)
+    # the segmenter's multi-scale deformable attention (mal_amd/msda.py), the same way
+    if name in ("MSDeformAttn", "ms_deform_attn"):
+        from . import msda
+        return getattr(msda, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

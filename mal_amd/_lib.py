@@ -125,6 +125,8 @@ SIGNATURES = {
     "mal_match": (i32, [vp]),
     "mal_instances_workspace_bytes": (sz, [i32] * 8),
     "mal_instances": (i32, [vp]),
+    "mal_msda_fwd": (i32, [vp]),
+    "mal_msda_fused_fwd": (i32, [vp]),
 }
 
 class DynItem(C.Structure):
@@ -223,8 +225,15 @@ class InstancesArgs(C.Structure):
                 [("ws_bytes", sz), ("stream", vp)])
 
 
+class MsdaArgs(C.Structure):
+    """mal_msda_args (include/mal_hip.h)."""
+    _fields_ = ([(n, vp) for n in ("value", "spatial_shapes", "level_start_index", "sampling_locations", "attention_weights",
+                                   "reference_points")] +
+                [(n, i32) for n in ("N", "S", "M", "D", "L", "P", "Lq", "ref_dim")] + [("out", vp), ("stream", vp)])
+
+
 DR_MAX_ITERS = 4
-MATCH_MAX, MATCH_U8, MATCH_F32 = 128, 0, 1
+MATCH_MAX,MATCH_U8, MATCH_F32 = 128, 0, 1
 DR_NO_AUTOMASK, DR_NO_MOTION_MASK, DR_NOISE_PHILOX, DR_AVG, DR_NO_SSIM, DR_POSE_UPDATE = 1, 2, 4, 8, 16, 32
 DR_POSE_NOISE_KEY = 0x706f73655f757064
 MS_MAX_SCALES = 4
@@ -258,7 +267,8 @@ def load():
         fn.argtypes = args
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
-    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs, InstancesArgs)):
+    for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs, InstancesArgs,
+                                 MsdaArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

@@ -10,7 +10,7 @@ extern "C" const char* mal_strerror(int code) {
   switch (code) {
     case MAL_OK: return "ok";
     case MAL_EINVAL: return "invalid argument (null pointer, bad size, or a flag this entry point does not take)";
-    case MAL_ESHAPE: return "unsupported shape (needs H,W >= 2 and B*4*H*W < 2^31)";
+    case MAL_ESHAPE: return "unsupported shape (needs H,W >= 2 and B*4*H*W < 2^31; mal_msda_*: a size outside the bounds in mal_hip.h)";
     case MAL_EWORKSPACE: return "workspace too small (see mal_workspace_bytes)";
     case MAL_ELAUNCH: return "HIP kernel launch failed";
     case MAL_ENODEVICE: return "no HIP device";
@@ -30,6 +30,7 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 6: return sizeof(mal_eval_args);
     case 7: return sizeof(mal_match_args);
     case 8: return sizeof(mal_instances_args);
+    case 9: return sizeof(mal_msda_args);
     default: return 0;
   }
 }
