@@ -859,7 +859,10 @@ int mal_direct_align_update_bwd(const float* H, const float* b, const float* pos
  *               runs without MAL_STEP_MAIN_TEMPORAL, MAL_STEP_DUAL_DISTIL, ens_disp, with B <= 64; otherwise as 1;
  *               1: a launch each, every sample computed (same-binary A/B); 0: in line after the fused sweep, epilogue
  *               inside the pass (kept for A/B);
- * "side_order"  0|1 (default 0): 1 = of the forked passes the student's goes first, the ensemble pass behind it (slower);
+ * "side_order"  0..2 (default 0): 1 = of the forked passes the student's goes first, the ensemble pass behind it (slower);
+ *               2 = the merged launch of "student_overlap" 2 picks the arrangement on the device from the live samples:
+ *               as 0 when one resident round of wave slots holds the live tasks of both passes, otherwise the student's
+ *               tasks first and the ensemble pass behind them in 8-row segments (same results; a launch per pass: as 0);
  * "side_priority" 0|1 (default 0): 1 = the side stream is created with the device's lowest priority (slower); read only when
  *               a caller stream's side stream is first created;
  * "tail_overlap" 0|1 (default 1): a --temporal step's backward chain runs on the side stream behind the fused sweep, beside

@@ -147,6 +147,7 @@ __global__ __launch_bounds__(1024) void dyn_extents16_kernel(DynBatch bt) {
 // of larger magnitude (the first on a tie), halved and rounded half-to-even; columns alike; replace=1 zeroes |d| < 3
 MAL_DEV void instance_delta(const DynParams& p, int i, int* dx_out, int* dy_out) {
   int el[4], en[4];  // low, top, right, left of (last, next): max / min over the row bands
+#pragma unroll 1  // (one frame's 8 records in flight at a time: both frames' at once are 64 VGPRs, the callers' register peak)
   for (int which = 0; which < 2; ++which) {
     int* e = which ? en : el;
     for (int t = 0; t < 4; ++t) e[t] = (t & 1) ? 0x7fffffff : 0;
@@ -308,6 +309,33 @@ MAL_DEV unsigned bytes4_at(const uint8_t* row, int cs, int W) {
 MAL_DEV float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 MAL_DEV void st4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 
+// acc[k][ch] += img[ch][base + k] where bit k of `sel` is set (+0.0f elsewhere): 4 * C unconditional loads, then the additions
+template <int C>
+MAL_DEV void gather_add(float (&acc)[4][C], const float* __restrict__ img, int HW, unsigned sel, int base) {
+  // (a 32-bit byte offset per pixel on the channel's wave-uniform base -- dyn_check bounds H * W * 4 below 2^31 --: one
+  // address register per pixel instead of a 64-bit pair per load)
+  const char* plane[C];
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    plane[ch] = reinterpret_cast<const char*>(img + (size_t)ch * HW);
+    asm volatile("" : "+s"(plane[ch]));  // (kept in scalar registers: the compiler would add the plane stride per lane)
+  }
+  float v[4][C];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned off = (unsigned)(((sel >> k) & 1u) ? base + k : 0) * 4u;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) v[k][ch] = *(const __attribute__((address_space(1))) float*)(plane[ch] + off);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+      acc[k][ch] += ((sel >> k) & 1u) ? v[k][ch] : 0.f;
+      asm volatile("" : "+v"(acc[k][ch]));  // formed HERE: the staging values die before the caller's next gather is issued
+    }
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void dyn_synth_fwd4_kernel(DynBatch bt) {
   extern __shared__ int s_delta[];
@@ -327,9 +355,10 @@ __global__ __launch_bounds__(256) void dyn_synth_fwd4_kernel(DynBatch bt) {
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) { accl[k][ch] = 0.f; accn[k][ch] = 0.f; }
   for (int i = 0; i < p.num; ++i) {
-    const uint8_t* ml = p.mask_last + (size_t)s_row[2 * i] * HW;
-    const uint8_t* mn = p.mask_next + (size_t)s_row[2 * i + 1] * HW;
-    const int dx = s_delta[2 * i], dy = s_delta[2 * i + 1];
+    // (the instance's four staged integers are the same in every lane: held in scalar registers)
+    const uint8_t* ml = p.mask_last + (size_t)__builtin_amdgcn_readfirstlane(s_row[2 * i]) * HW;
+    const uint8_t* mn = p.mask_next + (size_t)__builtin_amdgcn_readfirstlane(s_row[2 * i + 1]) * HW;
+    const int dx = __builtin_amdgcn_readfirstlane(s_delta[2 * i]), dy = __builtin_amdgcn_readfirstlane(s_delta[2 * i + 1]);
     const int rl = r - dx, rn = r + dx;  // source rows of the "last" copy (moves by +d) and of the "next" copy (-d)
     const unsigned wa = *reinterpret_cast<const unsigned*>(ml + pix), wb = *reinterpret_cast<const unsigned*>(mn + pix);
     const unsigned sl_raw = bytes4_at(ml + (size_t)min(max(rl, 0), H - 1) * W, c - dy, W);
@@ -340,21 +369,11 @@ __global__ __launch_bounds__(256) void dyn_synth_fwd4_kernel(DynBatch bt) {
     any_l |= sl; any_n |= sn;
     if (__any((sl | sn) != 0u)) {
       const int bl = rl * W + (c - dy), bn = rn * W + (c + dy);
-      float vl[4][C], vn[4][C];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) {
-          vl[k][ch] = il[(size_t)ch * HW + (((sl >> k) & 1u) ? bl + k : 0)];
-          vn[k][ch] = in[(size_t)ch * HW + (((sn >> k) & 1u) ? bn + k : 0)];
-        }
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) {
-          accl[k][ch] += ((sl >> k) & 1u) ? vl[k][ch] : 0.f;
-          accn[k][ch] += ((sn >> k) & 1u) ? vn[k][ch] : 0.f;
-        }
+      // one frame after the other: only one frame's staging values are live at a time, which keeps the kernel at 64
+      // VGPRs -- what is left on a SIMD beside two resident waves of a marching pass (2 x 224 of 512)
+      gather_add<C>(accl, il, HW, sl, bl);
+      __builtin_amdgcn_sched_barrier(0);
+      gather_add<C>(accn, in, HW, sn, bn);
     }
   }
   unsigned fw = 0u;
@@ -364,29 +383,26 @@ __global__ __launch_bounds__(256) void dyn_synth_fwd4_kernel(DynBatch bt) {
            (((bg_n >> k) & 1u) << 4)) << (8 * k);
   *reinterpret_cast<unsigned*>(p.flags + pix) = fw;
   if (p.prefilled && !__any(region != 0u)) return;  // ori_* hold the images already
-  float ol[C][4], on[C][4];
+  // a channel at a time: its two quads are stored before the next channel's are formed (fewer values live at once)
+  const bool prefilled = p.prefilled != 0;
 #pragma unroll
   for (int ch = 0; ch < C; ++ch) {
     const float4 a = ld4(il + (size_t)ch * HW + pix), b = ld4(in + (size_t)ch * HW + pix);
     const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+    float ol[4], on[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const bool rg = (region >> k) & 1u;
-      ol[ch][k] = rg ? (((any_l >> k) & 1u) ? accl[k][ch] : (((bg_l >> k) & 1u) ? bv[k] : av[k])) : av[k];
-      on[ch][k] = rg ? (((any_n >> k) & 1u) ? accn[k][ch] : (((bg_n >> k) & 1u) ? av[k] : bv[k])) : bv[k];
+      ol[k] = rg ? (((any_l >> k) & 1u) ? accl[k][ch] : (((bg_l >> k) & 1u) ? bv[k] : av[k])) : av[k];
+      on[k] = rg ? (((any_n >> k) & 1u) ? accn[k][ch] : (((bg_n >> k) & 1u) ? av[k] : bv[k])) : bv[k];
     }
+    float* const dl = p.ori_last + (size_t)ch * HW + pix;
+    float* const dn = p.ori_next + (size_t)ch * HW + pix;
+    if (!prefilled) { st4(dl, ol); st4(dn, on); continue; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((region >> k) & 1u) { dl[k] = ol[k]; dn[k] = on[k]; }
   }
-  if (!p.prefilled) {
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) { st4(p.ori_last + (size_t)ch * HW + pix, ol[ch]); st4(p.ori_next + (size_t)ch * HW + pix, on[ch]); }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if ((region >> k) & 1u) {
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch) { p.ori_last[(size_t)ch * HW + pix + k] = ol[ch][k]; p.ori_next[(size_t)ch * HW + pix + k] = on[ch][k]; }
-    }
 }
 
 // the adjoint, same order of additions per pixel as dyn_synth_bwd_kernel

@@ -108,10 +108,12 @@ int march_launch(MarchParams& p, int flags, hipStream_t st);
 // samples whose per-sample scale (stu.sample_scale, decided on the device from the tensor's contents at run time) is not
 // exactly zero: such a sample's terms are all multiplied by that zero.  The dead samples' rows of stu.g_reproj, their
 // boundary scratch rows and their records in stu.block_sums are zero-filled; their rows of the two passes' min_reproj maps
-// are NOT written (the caller must not read them).  stu_first: which sub-pass takes the leading workgroups.  B <= 64.
+// are NOT written (the caller must not read them).  order (option "side_order"): 0 / 1 = the ensemble's / the student's tasks take
+// the leading workgroups; 2 = every wave picks the arrangement from the live set: that of 0 when one resident round holds the live
+// tasks of both sub-passes, otherwise the student's tasks first and the ensemble pass behind them in 8-row segments.  B <= 64.
 // march_pair_qualifies: whether the options / shape allow it (march_pair_launch returns MAL_EINVAL otherwise).
 bool march_pair_qualifies(int B, int H, int W);
-int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStream_t st);
+int march_pair_launch(MarchParams* ens, MarchParams& stu, int order, hipStream_t st);
 // the decomposition march_launch picks for (B,H,W) and `flags` on the current device
 void march_geometry(int B, int H, int W, int flags, int* strips, int* segs, int* rows);
 inline int march_tasks_per_sample(int B, int H, int W, int flags) {

@@ -1318,7 +1318,18 @@ __global__ __launch_bounds__(64, 2) void march_framed_lean_kernel(MarchParams p_
 // each sub-pass in the same XCD-striped order, and the surplus workgroups of the student's sub-pass store the zeros the dead
 // tasks would have left (gradient rows, boundary scratch rows, the sums' record) so that no consumer reads stale memory.
 // No inter-workgroup hand-off: a workgroup's work depends on its index and the scale tensor only.
-struct MarchPairParams { MarchParams ens, stu; int ens_blocks, stu_blocks, stu_first; };
+//
+// Two arrangements of the workgroups, chosen by every wave from the live set when `choose` is set (option "side_order" 2):
+//   A: the two sub-passes one behind the other in the order `stu_first` gives -- taken when the live tasks of both fit in ONE
+//      resident round (`slots` waves), and always when `choose` is 0;
+//   B: otherwise.  The student's tasks (the long ones: gradient iterations) take the leading workgroups, so that all of them
+//      are resident from the start, and the ensemble pass runs behind them from `ens_short` -- the same pass decomposed into
+//      SHORT segments, whose tasks free their slots early for the student's surplus and for the producer's kernels.  The
+//      ensemble pass is forward only, nothing reads its per-task sums, and its per-pixel map does not depend on where the
+//      segment boundaries fall, so every output of the step is the same in both arrangements.  The student's decomposition
+//      never moves: its boundary rows and partials are laid out per task.
+// The grid holds stu_blocks + max(ens_blocks, ens_short_blocks) workgroups; those past the arrangement's own count return.
+struct MarchPairParams { MarchParams ens, ens_short, stu; int ens_blocks, ens_short_blocks, stu_blocks, stu_first, choose, slots; };
 
 // sample number of the k-th set bit of `mask` (k < popcount, wave-uniform)
 MAL_DEV int nth_sample(unsigned long long mask, int k, int lane) {
@@ -1348,12 +1359,6 @@ __global__ __launch_bounds__(64, 2) void march_pair_kernel(MarchPairParams pk_ke
   typedef __attribute__((address_space(4))) const MarchPairParams CPair;
   CPair* const pk = (CPair*)__builtin_amdgcn_kernarg_segment_ptr();
   const int lane = threadIdx.x;
-  // the sub-pass of this workgroup (wave-uniform): option "side_order" decides which one holds the leading workgroups
-  const int first = pk->stu_first ? pk->stu_blocks : pk->ens_blocks;
-  const bool in_first = (int)blockIdx.x < first;
-  const bool student = in_first == (pk->stu_first != 0);
-  const int id = in_first ? (int)blockIdx.x : (int)blockIdx.x - first;
-  CMarchParams* const kp = student ? &pk->stu : &pk->ens;
   // the live samples: scale != 0, as the student's pass forms it (march_body: sscale)
   const int B = pk->stu.B;
   float sc = 1.0f;
@@ -1363,6 +1368,19 @@ __global__ __launch_bounds__(64, 2) void march_pair_kernel(MarchPairParams pk_ke
   }
   const unsigned long long all = B >= 64 ? ~0ull : (1ull << B) - 1ull;
   const unsigned long long live = __ballot(lane < B && !(sc == 0.0f)) & all;
+  // the arrangement (wave-uniform, the same in every workgroup: kernarg and the live set only): B when one resident round
+  // does not hold the live tasks of both sub-passes
+  const int per_b_ens = pk->ens_blocks ? pk->ens.strips * pk->ens.segs : 0;
+  const bool short_ens = pk->choose && __popcll(live) * (pk->stu.strips * pk->stu.segs + per_b_ens) > pk->slots;
+  const bool stu_first = short_ens || pk->stu_first != 0;
+  const int ens_blocks = short_ens ? pk->ens_short_blocks : pk->ens_blocks;
+  // the sub-pass of this workgroup (wave-uniform): which one holds the leading workgroups
+  const int first = stu_first ? pk->stu_blocks : ens_blocks;
+  const bool in_first = (int)blockIdx.x < first;
+  const bool student = in_first == stu_first;
+  const int id = in_first ? (int)blockIdx.x : (int)blockIdx.x - first;
+  if (id >= (student ? pk->stu_blocks : ens_blocks)) return;  // the grid fits either arrangement
+  CMarchParams* const kp = student ? &pk->stu : (short_ens ? &pk->ens_short : &pk->ens);
   const int per_b = kp->strips * kp->segs;
   const int n_live = __popcll(live) * per_b;       // live tasks of this sub-pass
   const int per_xcd_live = (n_live + 7) >> 3;
@@ -1372,7 +1390,7 @@ __global__ __launch_bounds__(64, 2) void march_pair_kernel(MarchPairParams pk_ke
     const int k = t / per_b;
     const int task = nth_sample(live, k, lane) * per_b + (t - k * per_b);
     if (student) march_body<true, false, false, false, false, false, false, kSpecStudentNoEpi>(&pk->stu, task);
-    else march_body<false, false, false, false, false, false, false>(&pk->ens, task);
+    else march_body<false, false, false, false, false, false, false>(kp, task);
     return;
   }
   if (!student) return;  // nothing reads a dead sample's ensemble map
@@ -1637,29 +1655,36 @@ MarchParams march_params(int B, int H, int W, float min_depth, float max_depth, 
 }
 
 // the task decomposition of a pass over (B,H,W) with `flags`: strips x segs tasks per sample, `rows` output rows each
-static void march_decompose(MarchParams& p, int flags) {
+// wave slots of one resident round of a marching kernel (two waves per SIMD): CUs x 4 SIMDs x 2
+// (option "device_cus" > 0 stands in for the queried count, without a device query)
+static int march_slots() {
+  static int queried = 0;
+  int slots = g_device_cus * 8;
+  if (slots <= 0) {
+    if (queried == 0) {
+      int dev = 0, cus = 256;
+      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+      (void)hipGetLastError();
+      if (cus <= 0) cus = 256;
+      queried = cus * 8;
+    }
+    slots = queried;
+  }
+  return slots;
+}
+// rows_given > 0: that row count instead of the options' (the short ensemble decomposition of march_pair_launch)
+static void march_decompose(MarchParams& p, int flags, int rows_given = 0) {
   const bool grad = flags & MAL_F_GRAD;
   const int cw = grad ? 60 : 62;
   p.strips = (p.W + cw - 1) / cw;
   int rows = grad ? g_march_rows : (g_march_rows_fwd > 0 ? g_march_rows_fwd : g_march_rows);
+  if (rows_given > 0) rows = rows_given;
   if (rows <= 0) {
     // Every task is one wavefront that lives for (rows + 2*halo) iterations and the kernel runs at two
     // waves per SIMD (<= 256 VGPRs): the shortest makespan is the smallest `rows` whose task count still
-    // fits in ONE resident round (CUs x 4 SIMDs x 2).  Measured on MI355X at B=12 192x640: rows 13
+    // fits in ONE resident round (march_slots).  Measured on MI355X at B=12 192x640: rows 13
     // (1980 tasks <= 2048) 124 us vs rows 16 135 us vs rows 12 (2112 tasks, two rounds) 164 us.
-    // (option "device_cus" > 0 stands in for the queried count, without a device query)
-    static int queried = 0;
-    int slots = g_device_cus * 8;
-    if (slots <= 0) {
-      if (queried == 0) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipGetLastError();
-        if (cus <= 0) cus = 256;
-        queried = cus * 8;
-      }
-      slots = queried;
-    }
+    const int slots = march_slots();
     rows = 8;
     while (rows < p.H && (long long)p.B * p.strips * ((p.H + rows - 1) / rows) > slots) ++rows;
   }
@@ -1807,10 +1832,12 @@ bool march_pair_qualifies(int B, int H, int W) {
   return g_march_lean && g_debug == 0 && B <= 64 && (long long)H * W * (kTexel * 4) < (1ll << 24);
 }
 // the ensemble pass (`ens` nullable: --no_ens) and the student's pass without epilogue as one launch over the tasks of the
-// samples whose scale (stu.sample_scale, read on the device) is not zero; stu_first: the student's tasks take the leading workgroups
-int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStream_t st) {
-  auto prep = [&](MarchParams& p, int flags) {
-    march_decompose(p, flags);
+// samples whose scale (stu.sample_scale, read on the device) is not zero; order = option "side_order": 1 the student's tasks take
+// the leading workgroups, 2 the kernel picks the arrangement from the live set (MarchPairParams)
+constexpr int kPairShortRows = 8;  // the workspace's minimum segment height (march_decompose)
+int march_pair_launch(MarchParams* ens, MarchParams& stu, int order, hipStream_t st) {
+  auto prep = [&](MarchParams& p, int flags, int rows_given = 0) {
+    march_decompose(p, flags, rows_given);
     p.debug = g_debug; p.flip_odd = g_march_flip; p.packed = 3;
   };
   auto plain = [](const MarchParams& p) {  // nothing of the other formulations' operands
@@ -1827,10 +1854,16 @@ int march_pair_launch(MarchParams* ens, MarchParams& stu, int stu_first, hipStre
   MarchPairParams pk;
   pk.stu = stu;
   pk.ens = ens ? *ens : stu;  // (no workgroup reads it when ens_blocks == 0)
+  pk.ens_short = pk.ens;      // the same pass in kPairShortRows-row segments (arrangement B)
+  if (ens) prep(pk.ens_short, 0, kPairShortRows);
   pk.ens_blocks = ens ? ens->per_xcd * 8 : 0;
+  pk.ens_short_blocks = ens ? pk.ens_short.per_xcd * 8 : 0;
   pk.stu_blocks = stu.per_xcd * 8;
-  pk.stu_first = stu_first ? 1 : 0;
-  hipLaunchKernelGGL(march_pair_kernel, dim3((unsigned)(pk.ens_blocks + pk.stu_blocks)), dim3(64), 0, st, pk);
+  pk.stu_first = order == 1 ? 1 : 0;
+  pk.choose = order == 2 ? 1 : 0;
+  pk.slots = march_slots();
+  const int ens_grid = pk.ens_blocks > pk.ens_short_blocks ? pk.ens_blocks : pk.ens_short_blocks;
+  hipLaunchKernelGGL(march_pair_kernel, dim3((unsigned)(pk.stu_blocks + ens_grid)), dim3(64), 0, st, pk);
   return launch_status();
 }
 
@@ -2017,7 +2050,7 @@ extern "C" int mal_set_option(const char* name, int value) {
   if (eq("sweeps_batched")) { g_sweeps_batched = value != 0; return MAL_OK; }
   if (eq("tail_overlap")) { g_tail_overlap = value != 0; return MAL_OK; }
   if (eq("dyn_small_blocks")) { g_dyn_small_blocks = value != 0; return MAL_OK; }
-  if (eq("side_order")) { g_side_order = value != 0; return MAL_OK; }
+  if (eq("side_order")) { if (value < 0 || value > 2) return MAL_EINVAL; g_side_order = value; return MAL_OK; }
   if (eq("side_priority")) { g_side_priority = value != 0; return MAL_OK; }  // read when a side stream is first created
   if (eq("temporal_spec")) { if (!kExp && value) return MAL_EINVAL; g_temporal_spec = value != 0; return MAL_OK; }
   if (eq("march3")) { if (!kExp && value) return MAL_EINVAL; g_march3 = value != 0; return MAL_OK; }

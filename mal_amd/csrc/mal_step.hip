@@ -43,7 +43,9 @@ opt_t g_side_priority{0};
 opt_t g_student_overlap{2};
 // option "side_order" 1: the student's pass first, the (lighter, forward-only) ensemble pass behind it -- the one that ends up
 // beside the fused sweep; 0: ensemble first.  1 measured slower: 0.3265 vs 0.3200 ms -- the producer's small kernels starve
-// beside a pass that holds every wave slot and all of the LDS
+// beside a pass that holds every wave slot and all of the LDS.  2: the merged launch of "student_overlap" 2 picks its arrangement
+// on the device from the number of live samples (march_pair_kernel: student first with a short-segment ensemble pass behind
+// it when one resident round does not hold both, the order of 0 otherwise); a launch per pass orders them like 0
 opt_t g_side_order{0};
 // option "tail_overlap": 1 = a --temporal step's backward chain (producer's backward -> teacher's gradient sweep) runs on the
 // library's side stream behind the FUSED SWEEP only, beside the epilogue and the reduction of the forward (in a captured graph
@@ -791,11 +793,12 @@ static int fork_ensemble(const mal_step_args* a, const StepWs& w, hipStream_t st
   };
   if (aug_skip_applies(a)) {  // both forked passes in one launch, augmented samples skipped
     MarchParams stu = student_params(a, w, nullptr, nullptr, w.multi_reproj, false), ens = ensemble_params(a, w, w.ens_reproj);
-    rc = march_pair_launch(ensemble_forked(a) ? &ens : nullptr, stu, g_side_order ? 1 : 0, ss->s);
-  } else {
-    if (g_side_order && student_forked(a)) rc = student();
+    rc = march_pair_launch(ensemble_forked(a) ? &ens : nullptr, stu, g_side_order, ss->s);
+  } else {  // a launch per pass: 2 orders them like 0
+    const bool stu_first = g_side_order == 1;
+    if (stu_first && student_forked(a)) rc = student();
     if (!rc && ensemble_forked(a)) rc = launch_ensemble(a, w, a->ens_reproj ? a->ens_reproj : w.ens_reproj, ss->s);
-    if (!rc && !g_side_order && student_forked(a)) rc = student();
+    if (!rc && !stu_first && student_forked(a)) rc = student();
   }
   if (hipEventRecord(ss->join, ss->s) != hipSuccess) return rc ? rc : MAL_ELAUNCH;
   ss->pending = true;  // whatever was enqueued on the side stream is joined before the step's buffers are reused
