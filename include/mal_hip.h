@@ -594,6 +594,35 @@ int mal_decoder_join_fwd(const float* x, const float* skip, float* out, int B, i
 int mal_decoder_join_bwd(const float* g_out, const float* x, float* gx, float* gskip, int B, int C, int Cs, int h, int w,
                          int up, int elu, void* stream);
 
+/* ---- the glue behind a ResNet convolution (mal_amd/networks.py BasicBlock, the encoders' stems) as TWO launches each way:
+ * nn.BatchNorm2d -> (+ residual) -> (ReLU), y = relu(gamma * (x - mean) * invstd + beta + residual), and its adjoint.
+ * x, residual (nullable), y, g_out, dx, dr (B,C,H,W) fp32 contiguous; gamma, beta, running_*, dgamma, dbeta (C) fp32;
+ * save_mean, save_invstd (C) fp64: the batch statistics stay fp64 from the first element to the last use, and every
+ * per-element expression is evaluated in fp64 on the fp32 operands and rounded once.
+ * training = 1: batch statistics (biased variance for y, save_mean and save_invstd = 1/sqrt(var + eps) written), and the
+ * module's side effects on the device: running_mean = (1-momentum)*running_mean + momentum*mean, running_var likewise with
+ * the UNBIASED variance, *num_batches_tracked += 1.  training = 0: mean = running_mean, invstd = 1/sqrt(running_var + eps),
+ * nothing but y is written (num_batches_tracked, save_*, ws may be NULL).  The statistics pass writes per-(channel, block)
+ * partials (n, mean, M2) to ws and the apply pass combines them in a fixed order (Chan's formula, fp64; no atomics:
+ * mal_amd/csrc/mal_bn.hip states the order), so equal inputs give equal bits.
+ * The adjoint (training statistics only): g' = relu ? g_out * [y > 0] : g_out on the saved OUTPUT y (read only with relu = 1),
+ * dbeta = sum g', dgamma = sum g' * xh, dx = gamma*invstd*(g' - dbeta/N - xh*dgamma/N), dr = g'; each of dx, dr, dgamma, dbeta
+ * is nullable and a NULL one is neither computed nor written (all four NULL: MAL_OK, no launch); with dx, dgamma and dbeta all
+ * NULL nothing is reduced and ws may be NULL.
+ * The planning function is pure host code: blocks per channel (a function of N = B*H*W: the largest power of two <= 32 that
+ * leaves each block 2048 elements) and the workspace both directions need for that shape; either output pointer nullable.
+ * MAL_EINVAL: a null required pointer, B, C, H or W < 1, a tensor of 2^31 elements or more (32-bit offsets), training or relu
+ * outside {0,1}, eps negative or not finite, momentum outside [0,1], N < 2 where batch statistics are taken (training forward;
+ * a backward that reduces).  MAL_EWORKSPACE: ws_bytes below what the planning function returns. */
+int mal_bn_join_plan(int B, int C, int H, int W, int* blocks_per_channel, size_t* ws_bytes);
+int mal_bn_join_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* running_mean,
+                    float* running_var, int64_t* num_batches_tracked, float* y, double* save_mean, double* save_invstd, int B,
+                    int C, int H, int W, double eps, double momentum, int training, int relu, void* ws, size_t ws_bytes,
+                    void* stream);
+int mal_bn_join_bwd(const float* g_out, const float* x, const float* y, const float* gamma, const double* save_mean,
+                    const double* save_invstd, float* dx, float* dr, float* dgamma, float* dbeta, int B, int C, int H, int W,
+                    int relu, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- N2: the temporal-hint producer's per-sample arithmetic, manydepth/dyn_utils.py:6-119 --------
  * (fill_dynamic_obj + generate_dynamic_instance), given the matched instance masks of the two warped frames
  * (num,H,W as bytes, non-zero = set; Mask2Former stays outside, the matcher is mal_match below).  Per instance the displacement

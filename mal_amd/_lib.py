@@ -106,6 +106,10 @@ SIGNATURES = {
     "mal_upsample_bilinear_adjoint": (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, vp]),
     "mal_decoder_join_fwd": (i32, [c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mal_decoder_join_bwd": (i32, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "mal_bn_join_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(sz)]),
+    "mal_bn_join_fwd": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, vp, c_fp, c_fp, c_fp, i32, i32, i32, i32, C.c_double, C.c_double, i32,
+                              i32, vp, sz, vp]),
+    "mal_bn_join_bwd": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, vp, sz, vp]),
     "mal_set_option": (i32, [C.c_char_p, i32]),
     "mal_get_option": (i32, [C.c_char_p, C.POINTER(i32)]),
     "mal_build_has_experiments": (i32, []),

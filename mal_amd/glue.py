@@ -4,10 +4,20 @@
 
 ``decoder_join`` is what ``networks.DepthDecoder(fused_glue=True)`` calls at its 11 padding sites.  CUDA/HIP float32
 tensors only; there is no CPU path -- a CPU tensor raises ``MalError``.
+
+And the glue behind a ResNet convolution as two HIP launches each way (mal_amd/csrc/mal_bn.hip):
+
+    F.relu(bn(x) + residual)                      bn an nn.BatchNorm2d, residual and the ReLU optional
+
+``bn_join`` is what ``networks.BasicBlock`` and the encoders' stems call with ``fused_glue`` set (20 sites per ResNet-18).
 """
 from __future__ import annotations
 
+import ctypes
+import functools
+
 import torch
+import torch.nn.functional as F
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
@@ -81,3 +91,136 @@ def decoder_join(x, skip=None, up=2, elu=True):
     if up not in (1, 2):
         raise L.MalError("decoder_join: up must be 1 or 2, got %r" % (up,))
     return DecoderJoinFn.apply(x, skip, up, elu)
+
+
+# ------------------------------------------------------------------ batch norm, residual add and ReLU behind a convolution
+@functools.lru_cache(maxsize=None)
+def bn_join_plan(B, C, H, W):
+    """-> (blocks per channel, workspace bytes) of mal_bn_join_fwd / _bwd for that shape: pure host code"""
+    blocks, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+    L.check(L.load().mal_bn_join_plan(int(B), int(C), int(H), int(W), ctypes.byref(blocks), ctypes.byref(nbytes)),
+            "mal_bn_join_plan")
+    return blocks.value, nbytes.value
+
+
+_BN_WS = {}
+
+
+def _bn_workspace(device, nbytes):
+    """the partials of one direction live from its first launch to its second, both on the current stream: one buffer per
+    (device, stream, size) serves every call, so the steady state allocates nothing"""
+    key = (device.index, _stream(), nbytes)
+    ws = _BN_WS.get(key)
+    if ws is None:
+        ws = _BN_WS[key] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    return ws
+
+
+def bn_join_fallback_reason(x, bn, residual=None):
+    """why ``bn_join`` runs the module's own ATen composition for these arguments instead of the kernels, or None"""
+    if x.dim() != 4:
+        return "x is not (B,C,H,W)"
+    if x.dtype != torch.float32:
+        return "dtype other than float32"
+    if not x.is_contiguous():
+        return "x is not contiguous NCHW"
+    if residual is not None and (residual.dtype != x.dtype or residual.shape != x.shape or residual.device != x.device
+                                 or not residual.is_contiguous()):
+        return "residual is not a contiguous float32 tensor of x's shape"
+    if not bn.affine or bn.weight is None or bn.bias is None:
+        return "affine=False"
+    if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+        return "track_running_stats=False"
+    if bn.momentum is None:
+        return "momentum=None (cumulative average)"
+    if not bn.training and torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (x, residual, bn.weight, bn.bias)):
+        return "eval mode with a gradient requested"
+    if x.numel() >= 2 ** 31:
+        return "2^31 elements or more"
+    return None
+
+
+def _bn_aten(x, bn, residual, relu):
+    out = bn(x)
+    if residual is not None:
+        out = out + residual
+    return F.relu(out) if relu else out
+
+
+def bn_join_fwd(x, bn, residual=None, relu=True):
+    """the two forward launches -> (y, save_mean, save_invstd); the saved statistics are (C) fp64, None in eval mode.  In training
+    mode the module's running statistics and num_batches_tracked are updated on the device."""
+    B, C, H, W = x.shape
+    training = bool(bn.training)
+    y = torch.empty_like(x)
+    save_mean = save_invstd = ws = None
+    nbytes = 0
+    if training:
+        save_mean, save_invstd = torch.empty((2, C), dtype=torch.float64, device=x.device)  # fp64 until their last use
+        nbytes = bn_join_plan(B, C, H, W)[1]
+        ws = _bn_workspace(x.device, nbytes)
+    L.check(L.load().mal_bn_join_fwd(_p(x), _p(residual), _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var),
+                                     _p(bn.num_batches_tracked) if training else None, _p(y), _p(save_mean), _p(save_invstd),
+                                     B, C, H, W, float(bn.eps), float(bn.momentum), int(training), int(bool(relu)), _p(ws),
+                                     nbytes, _stream()), "mal_bn_join_fwd")
+    return y, save_mean, save_invstd
+
+
+def bn_join_bwd(g_out, x, y, weight, save_mean, save_invstd, relu=True, need_x=True, need_r=True, need_w=True, need_b=True):
+    """the adjoint of the training-mode forward -> (dx, dr, dgamma, dbeta), None where not asked for.  ``y`` (the forward's
+    output) is read only with ``relu``; without it dr is the cotangent itself."""
+    g_out = _req(g_out, "g_out")
+    B, C, H, W = x.shape
+    dev = x.device
+    dx = torch.empty_like(x) if need_x else None
+    dr = None
+    if need_r:
+        dr = torch.empty_like(x) if relu else g_out
+    dw = db = None
+    if need_w and need_b:
+        dw, db = torch.empty((2, C), dtype=torch.float32, device=dev)
+    elif need_w or need_b:
+        dw, db = (torch.empty(C, dtype=torch.float32, device=dev) if need else None for need in (need_w, need_b))
+    ws, nbytes = None, 0
+    if need_x or need_w or need_b:
+        nbytes = bn_join_plan(B, C, H, W)[1]
+        ws = _bn_workspace(dev, nbytes)
+    if need_x or need_w or need_b or (need_r and relu):
+        L.check(L.load().mal_bn_join_bwd(_p(g_out), _p(x), _p(y) if relu else None, _p(weight), _p(save_mean), _p(save_invstd),
+                                         _p(dx), _p(dr) if relu else None, _p(dw), _p(db), B, C, H, W, int(bool(relu)), _p(ws),
+                                         nbytes, _stream()), "mal_bn_join_bwd")
+    return dx, dr, dw, db
+
+
+class BnJoinFn(Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, bn, relu):
+        y, save_mean, save_invstd = bn_join_fwd(x, bn, residual, relu)
+        ctx.relu = bool(relu)
+        if bn.training:  # the mask of the ReLU is read from y: autograd's version check refuses a later write in place
+            ctx.save_for_backward(x, y if relu else None, weight, save_mean, save_invstd)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dr, dw, db = bn_join_bwd(g_out, x, y, weight, save_mean, save_invstd, ctx.relu, need[0], need[1], need[2], need[3])
+        return dx, dr, dw, db, None, None
+
+
+def bn_join(x, bn, residual=None, relu=True):
+    """``F.relu(bn(x) + residual)`` for an ``nn.BatchNorm2d`` module ``bn`` (``residual`` and ``relu`` optional), the
+    module's running statistics and ``num_batches_tracked`` updated as the module does it -- also under ``no_grad``; once
+    differentiable in training mode.  Where the kernels do not apply (``bn_join_fallback_reason``) the module's own ATen
+    composition runs.  CPU tensors raise ``MalError``; one value per channel in training mode raises ``ValueError``."""
+    if not x.is_cuda or (residual is not None and not residual.is_cuda):
+        raise L.MalError("bn_join: expected CUDA/HIP tensors, got %s (mal_amd has no CPU fallback)"
+                         % (x.device if not x.is_cuda else residual.device,))
+    if bn_join_fallback_reason(x, bn, residual) is not None:
+        return _bn_aten(x, bn, residual, relu)
+    if bn.training and x.numel() // x.shape[1] == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (x.size(),))
+    return BnJoinFn.apply(x, residual, bn.weight, bn.bias, bn, relu)

@@ -26,10 +26,32 @@ from .layers import transformation_from_parameters
 
 
 # ------------------------------------------------------------------ ResNet-18 in torchvision's layout
+class _FusedGlueSwitch:
+    """``fused_glue`` of a module that holds ResNet blocks: read at forward time by the module's own stem, and handed down to
+    every BasicBlock below it when it is set (a block reads its own)."""
+
+    @property
+    def fused_glue(self):
+        return self.__dict__.get("_fused_glue", False)
+
+    @fused_glue.setter
+    def fused_glue(self, value):
+        self.__dict__["_fused_glue"] = bool(value)
+        for m in self.modules():
+            if isinstance(m, BasicBlock):
+                m.fused_glue = bool(value)
+
+
+# A downsample norm (no ReLU, no residual: one MIOpen launch each way) goes to bn_join only from this many elements on: at
+# B=12, 192x640 the two launches win at layer2's (2.9 M elements) and lose at layer3's and layer4's (1.5 M, 0.7 M) in both
+# directions (DESIGN.md 14, profiles/encoder_glue_ab.txt).  Every other site wins on the sum of its two directions.
+PLAIN_JOIN_MIN_ELEMS = 1 << 21
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, fused_glue=False):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
@@ -37,19 +59,37 @@ class BasicBlock(nn.Module):
         self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
         self.downsample = downsample
+        # read at forward time: every BatchNorm2d -> (+ identity) -> ReLU behind a convolution as two HIP launches each way
+        # (mal_amd.glue.bn_join) instead of three or four ATen/MIOpen passes; same modules, same state dict
+        self.fused_glue = fused_glue
+
+    def _forward_fused(self, x):
+        """the same function; bn_join's output is saved for the ReLU's mask, so self.relu (in place) never touches it"""
+        from .glue import bn_join
+        identity = x
+        if self.downsample is not None:
+            identity = self.downsample[0](x)
+            if identity.numel() >= PLAIN_JOIN_MIN_ELEMS:
+                identity = bn_join(identity, self.downsample[1], None, relu=False)
+            else:
+                identity = self.downsample[1](identity)
+        out = bn_join(self.conv1(x), self.bn1, None, relu=True)
+        return bn_join(self.conv2(out), self.bn2, identity, relu=True)
 
     def forward(self, x):
+        if self.fused_glue:
+            return self._forward_fused(x)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self.relu(out + identity)
 
 
-class ResNet18(nn.Module):
+class ResNet18(_FusedGlueSwitch, nn.Module):
     """torchvision.models.resnet18 (random init) with ``num_input_images`` stacked RGB frames
     (resnet_encoder.py:15-41): same attribute names, same initialisation."""
 
-    def __init__(self, num_input_images=1, num_classes=1000):
+    def __init__(self, num_input_images=1, num_classes=1000, fused_glue=False):
         super().__init__()
         self.inplanes = 64
         self.conv1 = nn.Conv2d(num_input_images * 3, 64, kernel_size=7, stride=2, padding=3, bias=False)
@@ -68,6 +108,7 @@ class ResNet18(nn.Module):
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
+        self.fused_glue = fused_glue
 
     def _make_layer(self, planes, blocks, stride=1):
         downsample = None
@@ -85,10 +126,18 @@ def _pretrained_unavailable(pretrained):
                                   "(resnet_encoder.py:57-62); load a state dict instead")
 
 
-class ResnetEncoder(nn.Module):
+def _stem(conv1, bn1, relu, x, fused):
+    """conv1 -> bn1 -> relu of a ResNet: the feature at half resolution"""
+    if fused:
+        from .glue import bn_join
+        return bn_join(conv1(x), bn1, None, relu=True)
+    return relu(bn1(conv1(x)))
+
+
+class ResnetEncoder(_FusedGlueSwitch, nn.Module):
     """resnet_encoder.py:362-400"""
 
-    def __init__(self, num_layers=18, pretrained=False, num_input_images=1, **kwargs):
+    def __init__(self, num_layers=18, pretrained=False, num_input_images=1, fused_glue=False, **kwargs):
         super().__init__()
         if num_layers != 18:
             raise NotImplementedError("MAL uses ResNet-18 everywhere (repdepth.py:41,52)")
@@ -98,12 +147,12 @@ class ResnetEncoder(nn.Module):
         for name, param in self.encoder.named_parameters():
             if "fc" in name:
                 param.requires_grad = False
+        self.fused_glue = fused_glue  # as BasicBlock.fused_glue, for the stem and the 8 blocks
 
     def forward(self, input_image):
         self.features = []
         x = (input_image - 0.45) / 0.225
-        x = self.encoder.bn1(self.encoder.conv1(x))
-        self.features.append(self.encoder.relu(x))
+        self.features.append(_stem(self.encoder.conv1, self.encoder.bn1, self.encoder.relu, x, self.fused_glue))
         self.features.append(self.encoder.layer1(self.encoder.maxpool(self.features[-1])))
         self.features.append(self.encoder.layer2(self.features[-1]))
         self.features.append(self.encoder.layer3(self.features[-1]))
@@ -111,12 +160,12 @@ class ResnetEncoder(nn.Module):
         return self.features
 
 
-class ResnetEncoderMatching(nn.Module):
+class ResnetEncoderMatching(_FusedGlueSwitch, nn.Module):
     """resnet_encoder.py:66-119 (construction), :121-150 (depth bins), :264-329 (forward).  The cost volume
     (:152-233) and its lowest_cost / confidence_mask (:296-312) run in ``mal_amd.costvol`` (two HIP launches)."""
 
     def __init__(self, num_layers, pretrained, input_height, input_width, min_depth_bin=0.1, max_depth_bin=20.0,
-                 num_depth_bins=96, adaptive_bins=False, depth_binning="linear"):
+                 num_depth_bins=96, adaptive_bins=False, depth_binning="linear", fused_glue=False):
         super().__init__()
         if num_layers != 18:
             raise NotImplementedError("MAL uses ResNet-18 everywhere")
@@ -137,6 +186,7 @@ class ResnetEncoderMatching(nn.Module):
                                          nn.ReLU(inplace=True))
         if not adaptive_bins:
             self.compute_depth_bins(min_depth_bin, max_depth_bin)
+        self.fused_glue = fused_glue  # as BasicBlock.fused_glue, for the stem and the 8 blocks
 
     def compute_depth_bins(self, min_depth_bin, max_depth_bin):
         lo, hi = float(min_depth_bin), float(max_depth_bin)
@@ -154,7 +204,10 @@ class ResnetEncoderMatching(nn.Module):
 
     def feature_extraction(self, image, return_all_feats=False):
         image = (image - 0.45) / 0.225
-        feats_0 = self.layer0(image)
+        if self.fused_glue:  # around the Sequential of layer0, whose modules keep their names; layer1's blocks read their own switch
+            feats_0 = _stem(self.layer0[0], self.layer0[1], self.layer0[2], image, True)
+        else:
+            feats_0 = self.layer0(image)
         feats_1 = self.layer1(feats_0)
         return [feats_0, feats_1] if return_all_feats else feats_1
 
@@ -295,11 +348,12 @@ class RepDepth(nn.Module):
                                              input_height=opt.height, input_width=opt.width, adaptive_bins=True,
                                              min_depth_bin=0.1, max_depth_bin=20.0,
                                              depth_binning=g("depth_binning", "linear"),
-                                             num_depth_bins=g("num_depth_bins", 96))
+                                             num_depth_bins=g("num_depth_bins", 96), fused_glue=g("fused_encoder", False))
         self.depth = DepthDecoder(self.encoder.num_ch_enc, g("scales", [0]), fused_glue=g("fused_decoder", False))
-        self.mono_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained")
+        self.mono_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", fused_glue=g("fused_encoder", False))
         self.mono_depth = DepthDecoder(self.mono_encoder.num_ch_enc, g("scales", [0]), fused_glue=g("fused_decoder", False))
-        self.pose_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", num_input_images=2)
+        self.pose_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", num_input_images=2,
+                                          fused_glue=g("fused_encoder", False))
         self.pose = PoseDecoder(self.pose_encoder.num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
         self.matching_ids = [0]
         if g("use_future_frame", False):
