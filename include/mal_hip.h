@@ -278,6 +278,13 @@ enum {
                                buffers); elsewhere they are by definition the warped images mal_loss_step_warp wrote
                                (warp_*, still set), which the sweep reads there.  warp2_* may then be NULL: the pass in
                                front of the producer writes the warped images once instead of twice. */
+  MAL_STEP_GSYN_SPARSE = 8192, /* with MAL_STEP_SYN_SPARSE: the caller vouches that NOTHING reads g_syn_* densely -- the producer's
+                               backward turns those very buffers into g_warp_* in place (g_warp_* == g_syn_* in _bwd, MAL_EINVAL
+                               otherwise), reading the g_syn_region_* snapshots and writing region pixels only.  mal_loss_step_fwd
+                               then leaves the pixels of g_syn_* whose tile (60 columns x "syn_rows" rows) keeps more than two
+                               pixels away from the region UNWRITTEN -- their gradient is zero, and the teacher's gradient sweep
+                               of _bwd skips them by the workspace's tile map instead of reading zeros back.  Without the flag
+                               g_syn_* is dense (the zero-fill); the A/B switch is the flag itself. */
   MAL_STEP_MAIN_TEMPORAL = 128, /* --main_temporal (manydepth/trainer.py:1164, loss_utils.py:152-155): the STUDENT's pass takes the
                                hint as well -- its own warped images go through the producer and r(syn_f, target) joins the
                                student's per-pixel min (weight: consistency x matching x (1 - augmentation), unchanged).  With

@@ -14,7 +14,14 @@ noise_seed
     key of the "philox" stream (per rank: add the rank).
 consistency_target
     write ``outputs["consistency_target/0"]`` (loss_utils.py:212-215, a logging-only map).
+syn_grad_sparse
+    whole-step API with ``--temporal``: True (default) lets the step keep the cotangent of the synthesised pair sparse
+    (MAL_STEP_GSYN_SPARSE) where ``mal_amd.step`` can prove that nothing reads it densely; False: the dense zero-fill
+    (same-box A/B: ``MAL_SYN_GRAD_SPARSE=0`` in the environment sets the initial value).  Results are bit-identical.
 """
+import os
+
 noise_source = "cpu"
 noise_seed = 0x4d414c5eed
 consistency_target = True
+syn_grad_sparse = os.environ.get("MAL_SYN_GRAD_SPARSE", "1") != "0"

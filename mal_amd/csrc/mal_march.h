@@ -75,6 +75,11 @@ struct MarchParams {
   // min are warped with two DIFFERENT disparities -- frame -1 with disp, frame +1 with disp2): g_reproj receives d / d disp
   // (what frame -1's candidate contributes), g_reproj2 d / d disp2 (frame +1's); bnd2 = the boundary scratch rows of g_reproj2
   int framed; float* g_reproj2; float* bnd2;
+  // TEMPORAL gradient passes, nullable: g_color holds values only in the LIVE tiles of the fused sweep that wrote it -- one
+  // byte per task of that sweep, [B][live_segs][live_strips], tiles of live_rows rows x 60 columns (the gradient passes'
+  // own strips), 0 = the sweep stored nothing there and the cotangent is zero: the six loads of a gradient row in a dead
+  // tile are skipped.  The task's gradient rows (rows + 2 with the one-row halo) must fit a 64-bit row mask.
+  const unsigned char* g_color_live; int live_rows, live_strips, live_segs;
 };
 constexpr int kDecPlanes = MAL_DEC_PLANES;
 
@@ -121,6 +126,9 @@ inline int march_tasks_per_sample(int B, int H, int W, int flags) {
   march_geometry(B, H, W, flags, &strips, &segs, nullptr);
   return strips * segs;
 }
+// whether a gradient pass of `rows`-row tasks can take a liveness map (MarchParams::g_color_live): its gradient rows -- the
+// task's own and one boundary row at each end -- are looked up in a 64-bit row mask
+inline bool march_live_rows_fit(int rows) { return rows + 2 <= 64; }
 // the one-call steps: the first call of a step records the decomposition it uses for workspace `ws`; the later calls check
 // that the options still give the same one (MAL_ESTALE otherwise)
 void step_geom_record(const void* ws, int B, int H, int W);
@@ -181,7 +189,13 @@ struct FusedMoreArgs {
   const float* prev_min; const uint8_t* prev_arg; float* min_reproj; uint8_t* argmin; float* weight_out; double* block_sums;
   float* g_cand0; float* g_cand1; const uint8_t* region; float* g_region0; float* g_region1; const float* orig0; const float* orig1;
   size_t orig_stride; int weight_given;
+  // nullable, with a region map: one byte per task of the sweep ([B][segs][strips], photo_march_fused_geometry), written by
+  // every task: 1 = it did the full work, 0 = the region does not come near its tile -- and such a task then stores NOTHING
+  // into g_cand0 / g_cand1 (its pixels' gradient is zero; the reader consults the map instead of reading zeros back)
+  uint8_t* tile_live;
 };
+// the decomposition a sweep of (B,H,W) takes with / without a region map (the tile geometry of FusedMoreArgs::tile_live)
+void photo_march_fused_geometry(int B, int H, int W, bool region, int* strips, int* segs, int* rows);
 int photo_march_fused_more(const FusedMoreArgs& a, int B, int H, int W, int* per_sample_out, hipStream_t st,
                            unsigned* order = nullptr, unsigned* order_count = nullptr);
 int photo_march_fused_more_n(int n, const FusedMoreArgs* a, int B, int H, int W, int* per_sample_out, hipStream_t st);

@@ -571,6 +571,16 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     return m;
   };
   auto row_of = [&](int rr) { return min(max(reflect1(rr, H), 0), H - 1); };
+  // TEMPORAL with a liveness map of g_color (MarchParams::g_color_live): bit k = physical row ph_lo - 1 + k of this strip
+  // lies in a tile the fused sweep wrote (the task's gradient rows are [ph_lo - 1, ph_hi]: the launch checks that they fit).
+  // Lane k fetches row k's byte once, up front; the ballot keeps the verdicts in a scalar register pair.  Lanes 0, 1, 62
+  // and 63 read columns of the NEIGHBOURING strips' tiles under this strip's verdict -- possibly never-written memory -- but
+  // g[] of the gradient row is consumed per lane, under out_x only (pose partials, the stores): nothing of theirs leaves.
+  unsigned long long live_rows = ~0ull;
+  if (TEMPORAL && p.g_color_live) {
+    const int yy = min(max(ph_lo - 1 + lane, 0), H - 1);
+    live_rows = __ballot(p.g_color_live[(b * p.live_segs + yy / p.live_rows) * p.live_strips + strip] != 0);
+  }
   // everything iteration `rr` will need
   auto request = [&](const Maps& pp, int rr, Ahead& a) {
     // No branches here: a fixed number of loads lets the compiler count exactly how many are younger than the
@@ -598,12 +608,20 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
       a.noise = (float)*(pp.forced_arg + (oc >> 2));
       // (kernel-argument pointer) + (32-bit offset holding sample and channel: a (B,3,H,W) image is below 2^32 bytes) -- with
       // a pointer per plane the compiler, out of scalar registers, formed six 64-bit vector addresses per row and spilled
-      const unsigned og = moff(min(max(rr - 2, 0), H - 1)) + 2u * (unsigned)b * (unsigned)HW * 4u;  // pixel (b, 0, y, x) of a (B,3,H,W) image
+      const int gq = min(max(rr - 2, 0), H - 1);  // the gradient row
+      const unsigned og = moff(gq) + 2u * (unsigned)b * (unsigned)HW * 4u;  // pixel (b, 0, y, x) of a (B,3,H,W) image
+      // (the one branch of this block: wave-uniform, and these loads are older than the gathers, whose wait counts the
+      // YOUNGER ones only.  A row outside [ph_lo - 1, ph_hi] gets some other row's verdict: its values are never used)
+      if ((live_rows >> ((prow(gq) - (ph_lo - 1)) & 63)) & 1ull) {
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const unsigned o = og + (unsigned)ch * (unsigned)HW * 4u;
+        for (int ch = 0; ch < 3; ++ch) {
+          const unsigned o = og + (unsigned)ch * (unsigned)HW * 4u;
 #pragma unroll
-        for (int f = 0; f < 2; ++f) a.gc[f * 3 + ch] = ldf(pp.gcol[f], o);
+          for (int f = 0; f < 2; ++f) a.gc[f * 3 + ch] = ldf(pp.gcol[f], o);
+        }
+      } else {  // a dead tile of the fused sweep: nothing was stored there, the cotangent is zero
+#pragma unroll
+        for (int i = 0; i < 6; ++i) a.gc[i] = 0.f;
       }
     }
     a.ext = 1.f; a.mono = 0.f; a.cost = 1.f;
@@ -1717,6 +1735,10 @@ int march_launch(MarchParams& p, int flags, hipStream_t st) {
   if (p.color_out[0] && (long long)p.B * (p.color_out_stride ? (long long)p.color_out_stride : 3ll * p.H * p.W) * 4 >= (1ll << 32))
     return MAL_ESHAPE;  // the exported planes are addressed with 32-bit byte offsets
   if (p.forced_w && (long long)p.B * 3 * p.H * p.W * 4 >= (1ll << 32)) return MAL_ESHAPE;  // ... and so are the (B,3,H,W) colour cotangents
+  // the liveness map of the colour cotangents: a gradient pass's own strips, tiles of whole rows, a row mask of 64 bits
+  if (p.g_color_live && (!p.forced_w || !grad || p.live_rows < 1 || p.live_strips != p.strips ||
+                         p.live_segs != (p.H + p.live_rows - 1) / p.live_rows || !march_live_rows_fit(p.rows)))
+    return MAL_EINVAL;
   if (!p.cam_ready) {
     hipLaunchKernelGGL(cam_setup_kernel, dim3(p.B), dim3(64), 0, st, p.K, p.T[0], p.T[1], p.invK, p.cam);
     p.cam_ready = 1;
@@ -1970,8 +1992,10 @@ int warp_scales_launch(const WarpScaleMaps& m, const float* const src[2], const 
 // What the first call used is kept per workspace; a later call that would use another one is refused (MAL_ESTALE).
 struct StepGeom {
   int rows_grad, rows_fwd, pack_rows, halo1;
+  int syn_rows;  // the fused sweep's tiles: _fwd leaves its verdicts per tile, the gradient sweep of _bwd looks them up
   bool operator==(const StepGeom& o) const {
-    return rows_grad == o.rows_grad && rows_fwd == o.rows_fwd && pack_rows == o.pack_rows && halo1 == o.halo1;
+    return rows_grad == o.rows_grad && rows_fwd == o.rows_fwd && pack_rows == o.pack_rows && halo1 == o.halo1 &&
+           syn_rows == o.syn_rows;
   }
 };
 static StepGeom step_geom_now(int B, int H, int W) {
@@ -1980,6 +2004,7 @@ static StepGeom step_geom_now(int B, int H, int W) {
   march_geometry(B, H, W, 0, nullptr, nullptr, &g.rows_fwd);
   g.pack_rows = g_pack_rows;
   g.halo1 = g_march_halo1;
+  g.syn_rows = g_syn_rows;
   return g;
 }
 static std::mutex g_geom_mutex;

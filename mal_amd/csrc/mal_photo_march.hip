@@ -54,6 +54,9 @@ struct PhotoMarchParams {
   // orig_stride floats between samples.  (The whole-step API: the pass in front of the producer then writes the warped
   // images once instead of twice, and the producer touches its regions only.)
   const float* orig[2]; size_t orig_stride;
+  // FUSED with a region map, nullable: every task's verdict, [task] bytes (1 = full work, 0 = the region does not come near
+  // the tile); with it a task of the second kind stores no gradient at all (FusedMoreArgs::tile_live)
+  uint8_t* tile_live;
 };
 
 struct Px9 { float t[3], a[3], c[3]; };
@@ -192,8 +195,14 @@ __global__ __launch_bounds__(64, 4) void photo_march_fwd_kernel(PhotoMarchParams
 // the window sums are direction-symmetric and these kernels do not flip), so the outputs must not alias prev_min /
 // prev_arg.  The outputs (min_reproj / argmin / weight_out) ARRIVE holding the decision over the earlier candidates
 // (the pass in front of the producer wrote them, with its sums): this sweep overwrites them only at the pixels it
-// re-decides and leaves per-task DIFFERENCES of sum(rp*w), sum(w) -- a task the producer's region does not reach
-// writes zero gradients, zero differences and nothing else.
+// re-decides and leaves per-task DIFFERENCES of sum(rp*w), sum(w).  A task the producer's region does not come within two
+// pixels of (a DEAD tile) touches none of those outputs and leaves zero differences; its pixels' gradient is zero, and who
+// owns those pixels of g_cand depends on tile_live:
+//   null   the task stores the zeros itself: g_cand is dense after the sweep, any reader may take it as a whole
+//   given  the task stores only its verdict (tile_live[task] = 0; a live task stores 1) and NOTHING into g_cand: those
+//          pixels stay whatever the buffer held, and belong to nobody -- the one reader (the TEMPORAL gradient sweep,
+//          MarchParams::g_color_live) consults the map and never loads them; the producer's region-only backward reads the
+//          g_region snapshot and writes region pixels only, all of which lie in live tiles.
 // slot: the parameter block's index inside the kernel's argument (the batched launch: one block per scale)
 template <bool FUSED>
 MAL_DEV void photo_march_bwd_task(const PhotoMarchParams& p, const int task, const int slot = 0) {
@@ -243,7 +252,9 @@ MAL_DEV void photo_march_bwd_task(const PhotoMarchParams& p, const int task, con
 #pragma unroll 8
     for (int rr = max(y_lo - 2, 0); rr <= min(y_hi + 1, H - 1); ++rr) any |= rgn0[rr * W + gxr];
     if (!__any((any & 1u) && in_x)) {
-      if (out_x)
+      if (p.tile_live) {  // the verdict instead of the zeros: the reader skips this tile
+        if (lane == 0) p.tile_live[task] = 0;
+      } else if (out_x)
         for (int c = y_lo; c < y_hi; ++c) {
           const unsigned o0 = (unsigned)(c * W + gxr) * 4u + img_b, o1 = o0 + hw4, o2 = o1 + hw4;
           stf(p.g_cand[0], o0, 0.f); stf(p.g_cand[0], o1, 0.f); stf(p.g_cand[0], o2, 0.f);
@@ -253,6 +264,7 @@ MAL_DEV void photo_march_bwd_task(const PhotoMarchParams& p, const int task, con
       return;
     }
   }
+  if (FUSED && p.tile_live && lane == 0) p.tile_live[task] = 1;
   float nfA = 0.f, nfB = 0.f;  // region within one column, of rows r-2 and r-1
   const int r_first = max(y_lo - HALO, -1), r_last = y_hi - 1 + HALO;
   Px9 nxt;
@@ -752,6 +764,12 @@ int photo_march_bwd(const float* target, const float* const* cand, int n_cand, c
 // argmin / weight_out arrive holding the decision over the earlier candidates and are overwritten where this pair is
 // re-decided; per-task partials [task][2] = DIFFERENCES of sum(rp*w), sum(w) against that earlier decision; and
 // d sum(rp*w) / d candidate, unnormalised.  The checks and the kernel's parameter block of one sweep:
+// with a region map the few tasks that do the full work set the kernel's duration (every task is resident at once, and
+// a wavefront alone on its SIMD marches no faster): shorter tasks, four times as many (the workspace holds 2-row tasks)
+static void fused_decompose(PhotoMarchParams& p, bool region) {
+  if (region && g_syn_rows >= 2 && g_syn_rows < 8) decompose(p, 60, 8, g_syn_rows);
+  else decompose(p, 60, 2);
+}
 static int fused_more_params(PhotoMarchParams& p, const FusedMoreArgs& x, int B, int H, int W) {
   if (x.prev_min == x.min_reproj || x.prev_arg == x.argmin) return MAL_EINVAL;
   if (x.weight_given && x.noise) return MAL_EINVAL;
@@ -768,11 +786,18 @@ static int fused_more_params(PhotoMarchParams& p, const FusedMoreArgs& x, int B,
   p.g_cand[0] = x.g_cand0; p.g_cand[1] = x.g_cand1; p.region = x.region;
   p.orig[0] = x.orig0; p.orig[1] = x.orig1; p.orig_stride = orig_stride;
   if (x.region && x.g_region0 && x.g_region1) { p.g_region[0] = x.g_region0; p.g_region[1] = x.g_region1; }
-  // with a region map the few tasks that do the full work set the kernel's duration (every task is resident at once, and
-  // a wavefront alone on its SIMD marches no faster): shorter tasks, four times as many (the workspace holds 2-row tasks)
-  if (x.region && g_syn_rows >= 2 && g_syn_rows < 8) decompose(p, 60, 8, g_syn_rows);
-  else decompose(p, 60, 2);
+  if (x.tile_live && !x.region) return MAL_EINVAL;
+  p.tile_live = x.tile_live;
+  fused_decompose(p, x.region != nullptr);
   return MAL_OK;
+}
+void photo_march_fused_geometry(int B, int H, int W, bool region, int* strips, int* segs, int* rows) {
+  PhotoMarchParams p = {};
+  p.B = B; p.H = H; p.W = W;
+  fused_decompose(p, region);
+  if (strips) *strips = p.strips;
+  if (segs) *segs = p.segs;
+  if (rows) *rows = p.rows;
 }
 // one sweep; order (nullable): >= ntasks device words, order_count: two zeroed words
 int photo_march_fused_more(const FusedMoreArgs& a, int B, int H, int W, int* per_sample_out, hipStream_t st, unsigned* order,

@@ -68,6 +68,7 @@ struct StepWs {
   // temporal hint: winner of the four-way min (0/1 warped, 2/3 syn) and automask weight of the teacher, the
   // materialised-candidate kernel's per-task partials [task][2], what the step remembers between its calls
   unsigned char* arg_t; float* w_t; double* bs_ph;
+  unsigned char* tile_live;  // ... and that sweep's verdict per task ([B][segs][strips] in its decomposition): 1 = it wrote its tile of g_syn_*
   float* rp_warp; unsigned char* arg_warp;  // ... and min_f r(warp_f) / its winner as the pass in front of the producer leaves them
   // --main_temporal: the same for the student's pass (w_s: its weight = consistency x matching x (1 - augmentation), constant
   // under the four-way min; bs_s then holds the sums of the forward pass in front of the producer, bs_sh the sweep's differences)
@@ -116,6 +117,7 @@ static StepWs carve_step(void* base, int B, int H, int W) {
   w.cam = (float*)take((size_t)B * 40 * 4);
   w.bnd_t = (float*)take(march_bnd_floats(B, H, W) * 4);
   w.bnd_s = (float*)take(march_bnd_floats(B, H, W) * 4);
+  w.tile_live = (unsigned char*)take(nb * 4);  // tasks of >= 2 rows, as bs_ph
   w.bytes = o;
   return w;
 }
@@ -912,6 +914,17 @@ extern "C" int mal_loss_step_warp_scales(const mal_step_args* a, const mal_step_
 // syn+1], loss_utils.py:79-90,103), the automask and the teacher's sums are formed over all four, and the gradient w.r.t. the
 // synthesised images leaves unnormalised.  MAL_STEP_SYN_SPARSE: syn_* hold the synthesised images at the region pixels only;
 // elsewhere they are the warped images mal_loss_step_warp wrote (warp_*), which the sweep then reads instead
+// MAL_STEP_GSYN_SPARSE (with MAL_STEP_SYN_SPARSE): the cotangent g_syn_* stays sparse too -- the
+// sweep's dead tasks store their verdict in w.tile_live instead of zeros, and the teacher's gradient sweep of _bwd, the only
+// reader the caller vouches for, skips those tiles.  Both calls decide it here, from the flags and the decomposition (the
+// latter held by step_geom_check): the gradient sweep's tasks must fit its 64-bit row mask.
+static bool gsyn_sparse(const mal_step_args* a) {
+  const int need = MAL_STEP_TEMPORAL | MAL_STEP_SYN_SPARSE | MAL_STEP_GSYN_SPARSE;
+  if ((a->flags & need) != need || !a->syn_region || g_temporal_spec) return false;
+  int rows = 0;
+  march_geometry(a->B, a->H, a->W, MAL_F_GRAD, nullptr, nullptr, &rows);
+  return march_live_rows_fit(rows);
+}
 static FusedMoreArgs teacher_sweep(const mal_step_args* a, const StepWs& w, float* mono_reproj) {
   const bool sparse = (a->flags & MAL_STEP_SYN_SPARSE) != 0;
   FusedMoreArgs x = {};
@@ -920,6 +933,7 @@ static FusedMoreArgs teacher_sweep(const mal_step_args* a, const StepWs& w, floa
   x.block_sums = w.bs_ph; x.g_cand0 = a->g_syn_m1; x.g_cand1 = a->g_syn_p1; x.region = a->syn_region;
   x.g_region0 = a->g_syn_region_m1; x.g_region1 = a->g_syn_region_p1;
   x.orig0 = sparse ? a->warp_m1 : nullptr; x.orig1 = sparse ? a->warp_p1 : nullptr; x.orig_stride = (size_t)a->warp_sample_stride;
+  x.tile_live = gsyn_sparse(a) ? w.tile_live : nullptr;
   return x;
 }
 // --main_temporal: the student's pair joins ITS running min the same way; the weight is the pass's mask (w_s), whatever wins
@@ -1093,6 +1107,13 @@ static int launch_teacher_temporal(const mal_step_args* a, const StepWs& w, Side
   p.g_reproj = w.G_r_t; p.block_sums = w.bs_t;
   p.ident = w.ident;  // unused by the TEMPORAL instantiation (the launch checks the flag combination only)
   p.forced_w = w.w_t; p.forced_arg = w.arg_t; p.g_color[0] = a->g_warp_m1; p.g_color[1] = a->g_warp_p1;
+  if (gsyn_sparse(a)) {
+    // the fused sweep left its dead tiles of g_syn_* unwritten: only a producer whose backward turned those very buffers
+    // into g_warp_* in place, touching region pixels alone, may have set the flag -- anything else would be read as garbage
+    if (a->g_warp_m1 != a->g_syn_m1 || a->g_warp_p1 != a->g_syn_p1) return MAL_EINVAL;
+    p.g_color_live = w.tile_live;
+    photo_march_fused_geometry(a->B, a->H, a->W, true, &p.live_strips, &p.live_segs, &p.live_rows);
+  }
   if (g_temporal_spec) {
     // mal_loss_step_warp left the gradient as it is without the synthesised candidates: only the tasks near the region
     // map are redone (all of them without a map); the assembly finishes the teacher's gradient as in the plain step.

@@ -22,6 +22,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib as L
 from . import config, loss_utils, ops
 
+POISON_COTANGENTS = False  # tests: the cotangent buffers of a hinted step's synthesised pair start as NaN instead of uninitialised
 _NOISE_COUNTER = {}  # per device: the step number of the "philox" noise stream, a device word the step itself advances
 
 
@@ -306,7 +307,7 @@ class _Hint(_HintIO):
         new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
         super().__init__(a, student, scale, new((B, 2, 3, H, W)), [new((B, 3, H, W)) for _ in range(2)])
         self.sparse_flag = L.STEP_SYN_S_SPARSE if student else L.STEP_SYN_SPARSE
-        self.sparse = False
+        self.sparse, self.gsyn_sparse = False, False
         self.shape, self.dev = (B, 3, H, W), dev
         self.region, self.snap, self.syn, self.syn_data, self.leaf, self.g_syn = None, None, None, None, None, None
 
@@ -364,8 +365,37 @@ class _Hint(_HintIO):
             self._mark_sparse()
         # the cotangents of syn: this node's own buffers, which the producer's backward may turn into its result in place
         self.g_syn = [torch.empty(self.shape, dtype=torch.float32, device=self.dev) for _ in range(2)]
+        if POISON_COTANGENTS:
+            for g in self.g_syn:
+                g.fill_(float("nan"))
         self._set("syn", self.syn_data)
         self._set("g_syn", self.g_syn)
+        self.gsyn_sparse = self._cotangent_never_read_densely()
+        if self.gsyn_sparse:
+            self.a.flags |= L.STEP_GSYN_SPARSE
+
+    def _cotangent_never_read_densely(self):
+        """MAL_STEP_GSYN_SPARSE: may the fused sweep leave the tiles of g_syn away from the region unwritten?  Only when the
+        one reader besides the library's own gradient sweep provably touches region pixels alone: the teacher's pair at scale
+        0, a sparse producer with its region map (or no instance at all: the identity, nothing reads g_syn), both syn tensors
+        the outputs of ONE ``BatchSynthesisFn`` node whose image inputs are this hint's leaves themselves -- an autograd op
+        in between would be handed the cotangent as a whole -- and the snapshots its region-only backward gathers from."""
+        if not config.syn_grad_sparse or self.student or self.scale is not None or not self.sparse:
+            return False
+        if self.syn is None:
+            return True
+        return self.snap is not None and self._producer_on_leaves()
+
+    def _producer_on_leaves(self):
+        """both syn tensors are outputs of ONE ``BatchSynthesisFn`` node whose image inputs are this hint's leaves, nothing in
+        between: the producer's backward is then the only operation ``torch.autograd.grad`` runs"""
+        from . import dyn_utils
+        fn = self.syn[0].grad_fn
+        if fn is None or fn is not self.syn[1].grad_fn or not isinstance(fn, dyn_utils.BatchSynthesisFn._backward_cls):
+            return False
+        nxt = fn.next_functions
+        return len(nxt) >= 2 and all(nxt[i][0] is not None and getattr(nxt[i][0], "variable", None) is self.leaf[i]
+                                     for i in range(2))
 
     def expose(self, out, dense):
         self._expose(out, dense, self.syn_data if self.has_ins else None, self.region if self.sparse else None)
@@ -385,7 +415,10 @@ class _Hint(_HintIO):
             # mal_amd.dyn_utils.image_synthesis turns the cotangent buffers into its result in place
             reg = {g.data_ptr(): (self.snap[i] if self.snap is not None else None) for i, g in enumerate(self.g_syn)}
             dyn_utils.INPLACE_COTANGENTS.update(reg)
-            dyn_utils.BACKWARD_STREAM["handle"], dyn_utils.BACKWARD_STREAM["used"] = stream, False
+            # (the side stream only when that backward is ALL that runs: an autograd op behind it -- a producer that wraps
+            # image_synthesis -- runs on the caller's stream and would read the cotangents while the side stream still writes them)
+            dyn_utils.BACKWARD_STREAM["handle"] = stream if self._producer_on_leaves() else None
+            dyn_utils.BACKWARD_STREAM["used"] = False
             try:
                 g_warp = torch.autograd.grad(self.syn, self.leaf, self.g_syn, allow_unused=True)
             finally:
@@ -394,8 +427,13 @@ class _Hint(_HintIO):
                 used = dyn_utils.BACKWARD_STREAM["used"]
                 dyn_utils.BACKWARD_STREAM["handle"], dyn_utils.BACKWARD_STREAM["used"] = None, False
             # ... and only if the result IS those buffers (no further operation of the autograd engine on the caller's stream)
-            on_stream = bool(used) and all(g is not None and g.data_ptr() == q.data_ptr() and g.is_contiguous()
-                                           for g, q in zip(g_warp, self.g_syn))
+            in_place = all(g is not None and g.data_ptr() == q.data_ptr() and g.is_contiguous() for g, q in zip(g_warp, self.g_syn))
+            if self.gsyn_sparse and not in_place:
+                # the forward left the tiles of g_syn away from the region unwritten (MAL_STEP_GSYN_SPARSE): a backward that
+                # did not turn those very buffers into its result, region pixels only, has read memory nobody wrote
+                raise L.MalError("loss_step backward: the producer's backward did not take its in-place, region-only form, but "
+                                 "the step kept the cotangent of the synthesised pair sparse (config.syn_grad_sparse)")
+            on_stream = bool(used) and in_place
             g_warp = [torch.zeros_like(w) if g is None else g.contiguous() for g, w in zip(g_warp, self.warp)]
         self.g_warp = g_warp
         self._set("g_warp", g_warp)
