@@ -595,7 +595,13 @@ int mal_upsample_bilinear_adjoint(const float* g_out, int B, int h, int w, int H
  * {0,1} (0: no activation).  The adjoint is a gather in a fixed order (mal_amd/csrc/mal_glue.hip states it; no atomics,
  * no zero fill); it reads x only with elu = 1 (a' = x > 0 ? 1 : expm1f(x) + 1), and a NULL gx or gskip is not computed.
  * MAL_EINVAL: a null required pointer, up/elu out of range, B, C, h or w < 1, Cs < 0, Cs > 0 without skip, up*h < 2 or
- * up*w < 2 (reflection needs two rows), or a padded tensor of 2^31 elements or more (32-bit indices). */
+ * up*w < 2 (reflection needs two rows), or a padded tensor of 2^31 elements or more (32-bit indices).
+ * The planning function is pure host code with the same shape checks: the workgroups the forward launches for that shape,
+ * those of the adjoint that computes gx (need_x) and/or gskip (need_skip; ignored with Cs = 0; neither: 0 blocks, no
+ * launch), and the floats of the flat output one workgroup covers per sweep.  Both entry points take their grids from it;
+ * a grid that covers less than the output is strided over.  Every output pointer is nullable. */
+int mal_decoder_join_plan(int B, int C, int Cs, int h, int w, int up, int need_x, int need_skip, int* blocks_fwd,
+                          int* blocks_bwd, int* floats_per_block);
 int mal_decoder_join_fwd(const float* x, const float* skip, float* out, int B, int C, int Cs, int h, int w, int up, int elu,
                          void* stream);
 int mal_decoder_join_bwd(const float* g_out, const float* x, float* gx, float* gskip, int B, int C, int Cs, int h, int w,

@@ -106,6 +106,7 @@ SIGNATURES = {
     "mal_upsample_bilinear_adjoint": (i32, [c_fp, i32, i32, i32, i32, i32, c_fp, vp]),
     "mal_decoder_join_fwd": (i32, [c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mal_decoder_join_bwd": (i32, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "mal_decoder_join_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "mal_bn_join_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(sz)]),
     "mal_bn_join_fwd": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, vp, c_fp, c_fp, c_fp, i32, i32, i32, i32, C.c_double, C.c_double, i32,
                               i32, vp, sz, vp]),

@@ -34,6 +34,7 @@
 namespace mal {
 
 constexpr int kJoinBlocks = 2048;  // 256 CUs x 8 workgroups of 256 threads; more work is strided over
+constexpr int kJoinBlockFloats = 4 * 256;  // of the flat output, per workgroup and sweep
 
 // (d0 fastest) digits of a flat index over an array of shape (.., r2, r1, r0); d3 is the unbounded leading digit
 struct Odo { unsigned d0, d1, d2, d3; };
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(256) void join_bwd_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------------------- host
 static unsigned join_blocks(size_t n) {
-  const size_t b = (n + 1023) / 1024;  // 256 threads x 4 floats
+  const size_t b = (n + kJoinBlockFloats - 1) / kJoinBlockFloats;
   return (unsigned)(b < (size_t)kJoinBlocks ? (b ? b : 1) : (size_t)kJoinBlocks);
 }
 
@@ -261,9 +262,38 @@ static int join_check(int B, int C, int Cs, int h, int w, int up, int elu, size_
   return MAL_OK;
 }
 
+// the block counts of both launches, the one place they are decided (mal_decoder_join_plan reports them).  The backward's
+// two index spaces share one grid, sized by the larger of the outputs that are asked for; 0: nothing to launch
+struct JoinPlan {
+  size_t nx, ns;  // elements of gx and of gskip
+  unsigned blocks_fwd, blocks_bwd;
+};
+static JoinPlan join_plan(int B, int C, int Cs, int h, int w, int up, size_t n_out, bool need_x, bool need_skip) {
+  JoinPlan p;
+  p.nx = (size_t)B * C * h * w;
+  p.ns = (size_t)B * Cs * (size_t)(up * h) * (size_t)(up * w);
+  p.blocks_fwd = join_blocks(n_out);
+  const size_t most = (need_x ? p.nx : 0) > (need_skip ? p.ns : 0) ? p.nx : p.ns;
+  p.blocks_bwd = (need_x || need_skip) ? join_blocks(most) : 0u;
+  return p;
+}
+
 }  // namespace mal
 
 using namespace mal;
+
+extern "C" int mal_decoder_join_plan(int B, int C, int Cs, int h, int w, int up, int need_x, int need_skip, int* blocks_fwd,
+                                     int* blocks_bwd, int* floats_per_block) {
+  size_t n = 0;
+  const int rc = join_check(B, C, Cs, h, w, up, 0, &n);
+  if (rc) return rc;
+  if ((need_x != 0 && need_x != 1) || (need_skip != 0 && need_skip != 1)) return MAL_EINVAL;
+  const JoinPlan p = join_plan(B, C, Cs, h, w, up, n, need_x != 0, need_skip != 0 && Cs > 0);
+  if (blocks_fwd) *blocks_fwd = (int)p.blocks_fwd;
+  if (blocks_bwd) *blocks_bwd = (int)p.blocks_bwd;
+  if (floats_per_block) *floats_per_block = kJoinBlockFloats;
+  return MAL_OK;
+}
 
 extern "C" int mal_decoder_join_fwd(const float* x, const float* skip, float* out, int B, int C, int Cs, int h, int w, int up,
                                     int elu, void* stream) {
@@ -271,7 +301,7 @@ extern "C" int mal_decoder_join_fwd(const float* x, const float* skip, float* ou
   const int rc = join_check(B, C, Cs, h, w, up, elu, &n);
   if (rc) return rc;
   if (!x || !out || (Cs > 0 && !skip)) return MAL_EINVAL;
-  const unsigned blocks = join_blocks(n);
+  const unsigned blocks = join_plan(B, C, Cs, h, w, up, n, false, false).blocks_fwd;
   const JoinShape g = {(unsigned)C, (unsigned)Cs, (unsigned)h, (unsigned)w};
   const OdoSpace sp = odo_space((unsigned)(up * w + 2), (unsigned)(up * h + 2), (unsigned)(C + Cs), n, blocks, aligned16(out));
   hipStream_t st = (hipStream_t)stream;
@@ -290,9 +320,9 @@ extern "C" int mal_decoder_join_bwd(const float* g_out, const float* x, float* g
   if (!g_out || (elu && !x)) return MAL_EINVAL;
   if (Cs == 0) gskip = nullptr;
   if (!gx && !gskip) return MAL_OK;
-  const size_t nx = (size_t)B * C * h * w, ns = (size_t)B * Cs * (size_t)(up * h) * (size_t)(up * w);
-  const size_t most = (gx ? nx : 0) > (gskip ? ns : 0) ? nx : ns;
-  const unsigned blocks = join_blocks(most);
+  const JoinPlan p = join_plan(B, C, Cs, h, w, up, n, gx != nullptr, gskip != nullptr);
+  const size_t nx = p.nx, ns = p.ns;
+  const unsigned blocks = p.blocks_bwd;
   const JoinShape g = {(unsigned)C, (unsigned)Cs, (unsigned)h, (unsigned)w};
   const OdoSpace spx = odo_space((unsigned)w, (unsigned)h, (unsigned)C, nx, blocks, aligned16(gx) && (!elu || aligned16(x)));
   const OdoSpace sps = odo_space((unsigned)(up * w), (unsigned)(up * h), (unsigned)(Cs > 0 ? Cs : 1), ns, blocks, aligned16(gskip));

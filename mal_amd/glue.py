@@ -39,6 +39,17 @@ def _dims(x, skip, up):
     return B, C, Cs, h, w
 
 
+@functools.lru_cache(maxsize=None)
+def decoder_join_plan(B, C, Cs, h, w, up=2, need_x=True, need_skip=True):
+    """-> (workgroups of mal_decoder_join_fwd, workgroups of mal_decoder_join_bwd for those outputs, floats of the flat
+    output a workgroup covers per sweep) for that shape: pure host code.  A grid smaller than the output is strided over."""
+    fwd, bwd, per = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    L.check(L.load().mal_decoder_join_plan(int(B), int(C), int(Cs), int(h), int(w), int(up), int(bool(need_x)),
+                                           int(bool(need_skip)), ctypes.byref(fwd), ctypes.byref(bwd), ctypes.byref(per)),
+            "mal_decoder_join_plan")
+    return fwd.value, bwd.value, per.value
+
+
 def decoder_join_fwd(x, skip=None, up=2, elu=True):
     """-> (B, C+Cs, up*h+2, up*w+2): activation, nearest upsampling, concatenation and reflection padding in one launch"""
     x, skip = _req(x, "x"), _req(skip, "skip")
