@@ -99,15 +99,23 @@ def eigen_crop(h, w):
     return np.array([EIGEN_CROP[0] * h, EIGEN_CROP[1] * h, EIGEN_CROP[2] * w, EIGEN_CROP[3] * w]).astype(np.int32)
 
 
-def compute_errors(gt, pred):
-    """evaluate_depth.py:35-53 (numpy promotion decides every dtype)"""
+def _log(x, cr_log):
+    """np.log; with cr_log the log of a float32 array is the correctly rounded float32(log(float64(x))), which is what the
+    device computes (logf_cr), where numpy's SIMD logf is a few ulp off"""
+    if cr_log and np.asarray(x).dtype == np.float32:
+        return np.log(np.asarray(x).astype(np.float64)).astype(np.float32)
+    return np.log(x)
+
+
+def compute_errors(gt, pred, cr_log=False):
+    """evaluate_depth.py:35-53 (numpy promotion decides every dtype).  cr_log: see _log; it moves rmse_log only."""
     thresh = np.maximum((gt / pred), (pred / gt))
     a1 = (thresh < 1.25).mean()
     a2 = (thresh < 1.25 ** 2).mean()
     a3 = (thresh < 1.25 ** 3).mean()
     rmse = (gt - pred) ** 2
     rmse = np.sqrt(rmse.mean())
-    rmse_log = (np.log(gt) - np.log(pred)) ** 2
+    rmse_log = (_log(gt, cr_log) - _log(pred, cr_log)) ** 2
     rmse_log = np.sqrt(rmse_log.mean())
     abs_rel = np.mean(np.abs(gt - pred) / gt)
     sq_rel = np.mean(((gt - pred) ** 2) / gt)
@@ -138,10 +146,11 @@ def valid_points(gt_depth, split, min_depth=MIN_VAL, max_depth=MAX_VAL):
 
 
 def evaluate_image(gt_depth, pred_disp, split, median_scaling=True, scale_factor=None, min_depth=MIN_VAL,
-                   max_depth=MAX_VAL, fma_vertical=False, ulp=0, pointwise=True):
+                   max_depth=MAX_VAL, fma_vertical=False, ulp=0, pointwise=True, cr_log=False):
     """one image of Trainer.val (trainer.py:998-1051) for a float32 scaled disparity (h, w).  scale_factor None: the
     teacher's rule (no pred_depth_scale_factor).  ulp: move every resized disparity by that many ulps.  pointwise: resize
-    only at the valid points (same values as the full two-pass image, test_eval_oracle.py holds that).
+    only at the valid points (same values as the full two-pass image, test_eval_oracle.py holds that).  cr_log: as in
+    compute_errors.
     -> dict(errors, ratio (None without median scaling), pred (clamped, float32), gt (masked), n)"""
     win, (gh, gw), (ys, xs), mask = valid_points(gt_depth, split, min_depth, max_depth)
     if pointwise:
@@ -161,7 +170,7 @@ def evaluate_image(gt_depth, pred_disp, split, median_scaling=True, scale_factor
         pred *= ratio
     pred[pred < min_depth] = min_depth
     pred[pred > max_depth] = max_depth
-    return dict(errors=compute_errors(gt, pred), ratio=ratio, pred=pred, gt=gt, n=int(gt.size))
+    return dict(errors=compute_errors(gt, pred, cr_log), ratio=ratio, pred=pred, gt=gt, n=int(gt.size))
 
 
 def evaluate(gt_depths, disps, split, median_scaling=True, scale_factor=None, **kw):
