@@ -636,6 +636,28 @@ int mal_bn_join_bwd(const float* g_out, const float* x, const float* y, const fl
                     const double* save_invstd, float* dx, float* dr, float* dgamma, float* dbeta, int B, int C, int H, int W,
                     int relu, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the max-pool behind a ResNet stem (mal_amd/networks.py: the three encoders) as ONE launch each way:
+ * p = F.max_pool2d(y, kernel_size=3, stride=2, padding=1) and its adjoint.  y, g_y, dy (B,C,H,W) fp32 contiguous; p, g_p
+ * (B,C,OH,OW) fp32 and code (B,C,OH,OW) bytes, OH = (H-1)/2 + 1, OW = (W-1)/2 + 1.
+ * The winner of a window is ATen's: row-major over the window clipped to the plane, starting from -inf and the window's first
+ * element, a value replaces the running maximum when val > max || isnan(val) (the first of equal maxima wins; a NaN wins and
+ * a later NaN replaces it; a window of all -inf keeps its first element).  code, when not NULL, receives the winner's
+ * position in the UNCLIPPED window, kh*3 + kw in 0..8; with code NULL (no gradient wanted) only p is written.
+ * The adjoint is a gather over the codes: dy[h,w] = g_y[h,w] (+0 with g_y NULL: the cotangent that reaches y from its other
+ * consumer) plus g_p of each of the at most four windows whose code points at (h,w), added in ascending (oh, ow) -- a fixed
+ * order, no atomics, no zero fill, no read of y, no workspace; equal inputs give equal bits on either route.
+ * Routes: 4 outputs per thread forward when W % 8 == 0, y and p are 16-byte and code 4-byte aligned; 4 elements of dy per
+ * thread backward when W % 4 == 0, g_p, g_y and dy are 16-byte and code 4-byte aligned; one per thread otherwise.
+ * The planning function is pure host code with the same shape checks: the output size, the workgroups of either launch
+ * (256 threads; at most 2048, a larger tensor is strided over) and what a thread owns (4 or 1), for pointers that are
+ * (aligned = 1) or are not (0) aligned as above; every output pointer is nullable.
+ * MAL_EINVAL: a null required pointer (y, p; g_p, code, dy), B, C, H or W < 1, or y of 2^31 elements or more (32-bit offsets). */
+int mal_stem_pool_plan(int B, int C, int H, int W, int aligned, int* OH, int* OW, int* blocks_fwd, int* blocks_bwd,
+                       int* per_thread_fwd, int* per_thread_bwd);
+int mal_stem_pool_fwd(const float* y, float* p, uint8_t* code, int B, int C, int H, int W, void* stream);
+int mal_stem_pool_bwd(const float* g_p, const float* g_y, const uint8_t* code, float* dy, int B, int C, int H, int W,
+                      void* stream);
+
 /* ---- N2: the temporal-hint producer's per-sample arithmetic, manydepth/dyn_utils.py:6-119 --------
  * (fill_dynamic_obj + generate_dynamic_instance), given the matched instance masks of the two warped frames
  * (num,H,W as bytes, non-zero = set; Mask2Former stays outside, the matcher is mal_match below).  Per instance the displacement

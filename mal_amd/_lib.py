@@ -111,6 +111,9 @@ SIGNATURES = {
     "mal_bn_join_fwd": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, vp, c_fp, c_fp, c_fp, i32, i32, i32, i32, C.c_double, C.c_double, i32,
                               i32, vp, sz, vp]),
     "mal_bn_join_bwd": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "mal_stem_pool_plan": (i32, [i32, i32, i32, i32, i32] + [C.POINTER(i32)] * 6),
+    "mal_stem_pool_fwd": (i32, [c_fp, c_fp, vp, i32, i32, i32, i32, vp]),
+    "mal_stem_pool_bwd": (i32, [c_fp, c_fp, vp, c_fp, i32, i32, i32, i32, vp]),
     "mal_set_option": (i32, [C.c_char_p, i32]),
     "mal_get_option": (i32, [C.c_char_p, C.POINTER(i32)]),
     "mal_build_has_experiments": (i32, []),

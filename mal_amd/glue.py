@@ -10,6 +10,12 @@ And the glue behind a ResNet convolution as two HIP launches each way (mal_amd/c
     F.relu(bn(x) + residual)                      bn an nn.BatchNorm2d, residual and the ReLU optional
 
 ``bn_join`` is what ``networks.BasicBlock`` and the encoders' stems call with ``fused_glue`` set (20 sites per ResNet-18).
+
+And the max-pool behind the stem as one HIP launch each way (mal_amd/csrc/mal_pool.hip):
+
+    F.max_pool2d(y, kernel_size=3, stride=2, padding=1)
+
+``stem_pool`` is what the three encoders call with ``fused_pool`` set.
 """
 from __future__ import annotations
 
@@ -235,3 +241,108 @@ def bn_join(x, bn, residual=None, relu=True):
     if bn.training and x.numel() // x.shape[1] == 1:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (x.size(),))
     return BnJoinFn.apply(x, residual, bn.weight, bn.bias, bn, relu)
+
+
+# ------------------------------------------------------------------------------------ the 3x3 / 2 max-pool behind a stem
+@functools.lru_cache(maxsize=None)
+def stem_pool_plan(B, C, H, W, aligned=True):
+    """-> (OH, OW, workgroups forward, workgroups backward, outputs a thread owns forward, elements of dy a thread owns
+    backward) of mal_stem_pool_fwd / _bwd for that shape, with pointers that are (``aligned``) or are not on the 16-byte
+    grid: pure host code.  A grid smaller than the tensor is strided over."""
+    out = [ctypes.c_int(0) for _ in range(6)]
+    L.check(L.load().mal_stem_pool_plan(int(B), int(C), int(H), int(W), int(bool(aligned)), *[ctypes.byref(o) for o in out]),
+            "mal_stem_pool_plan")
+    return tuple(o.value for o in out)
+
+
+def _pool_shape(y):
+    if y.dim() != 4:
+        raise L.MalError("stem_pool: y must be (B,C,H,W), got %s" % (tuple(y.shape),))
+    B, C, H, W = y.shape
+    return B, C, H, W, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def stem_pool_fwd(y, need_code=True):
+    """-> (p, code): ``F.max_pool2d(y, 3, 2, 1)`` and, with ``need_code``, one byte per output: the winner's position kh*3 + kw
+    in the unclipped window (None otherwise: nothing is allocated for it)"""
+    y = _req(y, "y")
+    B, C, H, W, OH, OW = _pool_shape(y)
+    p = torch.empty((B, C, OH, OW), dtype=torch.float32, device=y.device)
+    code = torch.empty((B, C, OH, OW), dtype=torch.uint8, device=y.device) if need_code else None
+    L.check(L.load().mal_stem_pool_fwd(_p(y), _p(p), _p(code), B, C, H, W, _stream()), "mal_stem_pool_fwd")
+    return p, code
+
+
+def stem_pool_bwd(g_p, g_y, code, shape):
+    """the adjoint, gathered in a fixed order: (cotangent of p, cotangent that reaches y from its other consumer, the forward's
+    codes, y's shape) -> dy.  Either cotangent may be None; without ``g_p`` the result is ``g_y`` itself and nothing is launched."""
+    if g_p is None:
+        return g_y
+    g_p, g_y = _req(g_p, "g_p"), _req(g_y, "g_y")
+    B, C, H, W = shape
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if tuple(g_p.shape) != (B, C, OH, OW) or tuple(code.shape) != (B, C, OH, OW) or code.dtype != torch.uint8:
+        raise L.MalError("stem_pool_bwd: g_p and code must be %s, got %s and %s" % ((B, C, OH, OW), tuple(g_p.shape), tuple(code.shape)))
+    if g_y is not None and tuple(g_y.shape) != (B, C, H, W):
+        raise L.MalError("stem_pool_bwd: g_y must be %s, got %s" % ((B, C, H, W), tuple(g_y.shape)))
+    dy = torch.empty((B, C, H, W), dtype=torch.float32, device=g_p.device)
+    L.check(L.load().mal_stem_pool_bwd(_p(g_p), _p(g_y), _p(code), _p(dy), B, C, H, W, _stream()), "mal_stem_pool_bwd")
+    return dy
+
+
+class StemPoolFn(Function):
+    """y -> (y, p).  The input comes back as an output so that the cotangent of its other consumer (the decoder's skip) and the
+    pool's arrive together in one backward, which writes their sum in one pass; the codes are all it saves."""
+
+    @staticmethod
+    def forward(ctx, y):
+        ctx.set_materialize_grads(False)  # a missing cotangent arrives as None, not as a tensor of zeros
+        ctx.shape = tuple(y.shape)
+        p, code = stem_pool_fwd(y, need_code=True)
+        ctx.save_for_backward(code)
+        return y, p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_y, g_p):
+        (code,) = ctx.saved_tensors
+        return stem_pool_bwd(g_p, g_y, code, ctx.shape)
+
+
+def stem_pool_fallback_reason(y, pool=None):
+    """why ``stem_pool`` runs the module's own ``nn.MaxPool2d`` for these arguments instead of the kernels, or None"""
+    if pool is not None:
+        if type(pool) is not torch.nn.MaxPool2d:
+            return "not an nn.MaxPool2d"
+        pair = torch.nn.modules.utils._pair
+        for name, want in (("kernel_size", 3), ("stride", 2), ("padding", 1), ("dilation", 1)):
+            if tuple(pair(getattr(pool, name))) != (want, want):
+                return "%s other than %d" % (name, want)
+        if pool.ceil_mode:
+            return "ceil_mode=True"
+        if pool.return_indices:
+            return "return_indices=True"
+    if y.dim() != 4:
+        return "y is not (B,C,H,W)"
+    if y.dtype != torch.float32:
+        return "dtype other than float32"
+    if not y.is_contiguous():
+        return "y is not contiguous NCHW"
+    if y.numel() >= 2 ** 31:
+        return "2^31 elements or more"
+    return None
+
+
+def stem_pool(y, pool=None):
+    """-> (y, p) with ``p = F.max_pool2d(y, kernel_size=3, stride=2, padding=1)`` (``pool``: the ``nn.MaxPool2d`` module this
+    stands for).  Use the returned ``y`` wherever the stem feature goes besides the pool: with a gradient wanted it is an output
+    of the same autograd node, so both cotangents are summed by the pool's one backward pass; once differentiable.  Under
+    ``no_grad`` no codes are written.  Where the kernels do not apply (``stem_pool_fallback_reason``) the module's own call
+    runs.  CPU tensors raise ``MalError``."""
+    if not y.is_cuda:
+        raise L.MalError("stem_pool: expected a CUDA/HIP tensor, got %s (mal_amd has no CPU fallback)" % (y.device,))
+    if stem_pool_fallback_reason(y, pool) is not None:
+        return y, (pool(y) if pool is not None else F.max_pool2d(y, kernel_size=3, stride=2, padding=1))
+    if torch.is_grad_enabled() and y.requires_grad:
+        return StemPoolFn.apply(y)
+    return y, stem_pool_fwd(y, need_code=False)[0]

@@ -27,7 +27,7 @@ def default_options(**kw):
              num_matching_frames=1, use_future_frame=False, pose_cnn=False, dc=False, distil=True, no_ens=False,
              temporal=False, main_temporal=False, dual_distil=False, learn_ens=False, no_ssim=False, loss_blc=False,
              disable_automasking=False, no_matching_augmentation=False, notadabins=False, fused_decoder=False, fused_encoder=False,
-             learning_rate=1e-4,
+             fused_pool=False, learning_rate=1e-4,
              scheduler_step_size=15, warmup_steps=0, decay_steps=1000, freeze_teacher_epoch=15,
              num_train_data=39810)  # KITTI eigen_zhou train split size (splits/eigen_zhou/train_files.txt)
     o.update(kw)

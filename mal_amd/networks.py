@@ -89,7 +89,7 @@ class ResNet18(_FusedGlueSwitch, nn.Module):
     """torchvision.models.resnet18 (random init) with ``num_input_images`` stacked RGB frames
     (resnet_encoder.py:15-41): same attribute names, same initialisation."""
 
-    def __init__(self, num_input_images=1, num_classes=1000, fused_glue=False):
+    def __init__(self, num_input_images=1, num_classes=1000, fused_glue=False, fused_pool=False):
         super().__init__()
         self.inplanes = 64
         self.conv1 = nn.Conv2d(num_input_images * 3, 64, kernel_size=7, stride=2, padding=3, bias=False)
@@ -109,6 +109,14 @@ class ResNet18(_FusedGlueSwitch, nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         self.fused_glue = fused_glue
+        self.fused_pool = fused_pool  # read at forward time: the max-pool as one HIP launch each way (mal_amd.glue.stem_pool)
+
+    def forward(self, x):
+        """torchvision's ResNet.forward (the encoders below call the parts themselves)"""
+        x = _stem(self.conv1, self.bn1, self.relu, x, self.fused_glue)
+        x = _pool(self.maxpool, x, self.fused_pool)[1]
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
 
     def _make_layer(self, planes, blocks, stride=1):
         downsample = None
@@ -134,10 +142,20 @@ def _stem(conv1, bn1, relu, x, fused):
     return relu(bn1(conv1(x)))
 
 
+def _pool(maxpool, y, fused):
+    """the max-pool behind the stem -> (the stem feature to hand on, its pooled map).  Fused, the feature comes back as an output
+    of the pool's autograd node (mal_amd.glue.stem_pool), so the gradient of whoever else reads it -- the decoder's skip -- and
+    the pool's are summed in the pool's one backward pass instead of by a pass of autograd's own."""
+    if fused:
+        from .glue import stem_pool
+        return stem_pool(y, maxpool)
+    return y, maxpool(y)
+
+
 class ResnetEncoder(_FusedGlueSwitch, nn.Module):
     """resnet_encoder.py:362-400"""
 
-    def __init__(self, num_layers=18, pretrained=False, num_input_images=1, fused_glue=False, **kwargs):
+    def __init__(self, num_layers=18, pretrained=False, num_input_images=1, fused_glue=False, fused_pool=False, **kwargs):
         super().__init__()
         if num_layers != 18:
             raise NotImplementedError("MAL uses ResNet-18 everywhere (repdepth.py:41,52)")
@@ -148,12 +166,15 @@ class ResnetEncoder(_FusedGlueSwitch, nn.Module):
             if "fc" in name:
                 param.requires_grad = False
         self.fused_glue = fused_glue  # as BasicBlock.fused_glue, for the stem and the 8 blocks
+        self.fused_pool = fused_pool  # read at forward time, independent of fused_glue: the max-pool through mal_amd.glue.stem_pool
 
     def forward(self, input_image):
         self.features = []
         x = (input_image - 0.45) / 0.225
-        self.features.append(_stem(self.encoder.conv1, self.encoder.bn1, self.encoder.relu, x, self.fused_glue))
-        self.features.append(self.encoder.layer1(self.encoder.maxpool(self.features[-1])))
+        stem = _stem(self.encoder.conv1, self.encoder.bn1, self.encoder.relu, x, self.fused_glue)
+        stem, pooled = _pool(self.encoder.maxpool, stem, self.fused_pool)
+        self.features.append(stem)
+        self.features.append(self.encoder.layer1(pooled))
         self.features.append(self.encoder.layer2(self.features[-1]))
         self.features.append(self.encoder.layer3(self.features[-1]))
         self.features.append(self.encoder.layer4(self.features[-1]))
@@ -165,7 +186,7 @@ class ResnetEncoderMatching(_FusedGlueSwitch, nn.Module):
     (:152-233) and its lowest_cost / confidence_mask (:296-312) run in ``mal_amd.costvol`` (two HIP launches)."""
 
     def __init__(self, num_layers, pretrained, input_height, input_width, min_depth_bin=0.1, max_depth_bin=20.0,
-                 num_depth_bins=96, adaptive_bins=False, depth_binning="linear", fused_glue=False):
+                 num_depth_bins=96, adaptive_bins=False, depth_binning="linear", fused_glue=False, fused_pool=False):
         super().__init__()
         if num_layers != 18:
             raise NotImplementedError("MAL uses ResNet-18 everywhere")
@@ -187,6 +208,7 @@ class ResnetEncoderMatching(_FusedGlueSwitch, nn.Module):
         if not adaptive_bins:
             self.compute_depth_bins(min_depth_bin, max_depth_bin)
         self.fused_glue = fused_glue  # as BasicBlock.fused_glue, for the stem and the 8 blocks
+        self.fused_pool = fused_pool  # as ResnetEncoder.fused_pool
 
     def compute_depth_bins(self, min_depth_bin, max_depth_bin):
         lo, hi = float(min_depth_bin), float(max_depth_bin)
@@ -208,7 +230,11 @@ class ResnetEncoderMatching(_FusedGlueSwitch, nn.Module):
             feats_0 = _stem(self.layer0[0], self.layer0[1], self.layer0[2], image, True)
         else:
             feats_0 = self.layer0(image)
-        feats_1 = self.layer1(feats_0)
+        if self.fused_pool:  # around the Sequential of layer1 = (maxpool, layer1), whose modules keep their names
+            feats_0, pooled = _pool(self.layer1[0], feats_0, True)
+            feats_1 = self.layer1[1](pooled)
+        else:
+            feats_1 = self.layer1(feats_0)
         return [feats_0, feats_1] if return_all_feats else feats_1
 
     def forward(self, current_image, lookup_images, poses, K, invK, min_depth_bin=None, max_depth_bin=None):
@@ -348,13 +374,15 @@ class RepDepth(nn.Module):
                                              input_height=opt.height, input_width=opt.width, adaptive_bins=True,
                                              min_depth_bin=0.1, max_depth_bin=20.0,
                                              depth_binning=g("depth_binning", "linear"),
-                                             num_depth_bins=g("num_depth_bins", 96), fused_glue=g("fused_encoder", False))
+                                             num_depth_bins=g("num_depth_bins", 96), fused_glue=g("fused_encoder", False),
+                                             fused_pool=g("fused_pool", False))
         self.depth = DepthDecoder(self.encoder.num_ch_enc, g("scales", [0]), fused_glue=g("fused_decoder", False))
-        self.mono_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", fused_glue=g("fused_encoder", False))
+        self.mono_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", fused_glue=g("fused_encoder", False),
+                                          fused_pool=g("fused_pool", False))
         self.mono_depth = DepthDecoder(self.mono_encoder.num_ch_enc, g("scales", [0]), fused_glue=g("fused_decoder", False))
         self.pose_encoder = ResnetEncoder(18, g("weights_init", "scratch") == "pretrained", num_input_images=2,
-                                          fused_glue=g("fused_encoder", False))
-        self.pose = PoseDecoder(self.pose_encoder.num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
+                                          fused_glue=g("fused_encoder", False), fused_pool=g("fused_pool", False))
+        self.pose =PoseDecoder(self.pose_encoder.num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
         self.matching_ids = [0]
         if g("use_future_frame", False):
             self.matching_ids.append(1)
