@@ -787,7 +787,12 @@ int mal_instances(const mal_instances_args* args);
  * N, S, Lq >= 1, ref_dim 2 or 4 (fused), and value, out and sampling_locations below 2^31 elements each; anything else is
  * MAL_ESHAPE.  A null args or a null required pointer is MAL_EINVAL (checked first, before any HIP call).  float4 loads and
  * stores when D % 4 == 0 and value and out are 16-byte aligned, one channel per lane otherwise.  One launch on `stream`; no
- * workspace, no allocation, no atomics, bit-reproducible. */
+ * workspace, no allocation, no atomics, bit-reproducible.
+ * The planning function is pure host code with the same shape checks (MAL_ESHAPE for exactly the shapes both entry points
+ * refuse; ref_dim is not a shape): for value and out that are (aligned = 1) or are not (0) on the 16-byte grid, the channels
+ * a lane owns (4 or 1), the rows (n, q, m) a workgroup of 256 threads owns -- 256 / (D / vec), at most 4096 / (3 L P + 1) by
+ * the LDS budget, at most N Lq M --, the workgroups of the launch and its dynamic LDS bytes.  Both entry points take their
+ * launch from it; every output pointer is nullable. */
 typedef struct mal_msda_args {
   const float* value;               /* (N,S,M,D) */
   const int64_t* spatial_shapes;    /* device (L,2): H_l, W_l */
@@ -799,6 +804,8 @@ typedef struct mal_msda_args {
   float* out;                       /* (N,Lq,M*D) */
   void* stream;
 } mal_msda_args;
+int mal_msda_plan(int N, int S, int Lq, int M, int D, int L, int P, int aligned, int* vec, int* rows, int* blocks,
+                  size_t* lds_bytes);
 int mal_msda_fwd(const mal_msda_args* args);
 int mal_msda_fused_fwd(const mal_msda_args* args);
 

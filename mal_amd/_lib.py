@@ -133,6 +133,7 @@ SIGNATURES = {
     "mal_match": (i32, [vp]),
     "mal_instances_workspace_bytes": (sz, [i32] * 8),
     "mal_instances": (i32, [vp]),
+    "mal_msda_plan": (i32, [i32] * 8 + [C.POINTER(i32)] * 3 + [C.POINTER(sz)]),
     "mal_msda_fwd": (i32, [vp]),
     "mal_msda_fused_fwd": (i32, [vp]),
 }

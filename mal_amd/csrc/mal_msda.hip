@@ -166,41 +166,60 @@ __global__ __launch_bounds__(kMsdaThreads) void msda_fwd_kernel(MsdaParams p) {
 
 using namespace mal;
 
-static int msda_check(const mal_msda_args* a, bool fused) {
-  if (!a) return MAL_EINVAL;
-  if (!a->value || !a->spatial_shapes || !a->level_start_index || !a->sampling_locations || !a->attention_weights || !a->out)
-    return MAL_EINVAL;
-  if (fused && !a->reference_points) return MAL_EINVAL;
-  if (a->N < 1 || a->S < 1 || a->Lq < 1 || a->M < 1) return MAL_ESHAPE;
-  if (a->L < 1 || a->L > MAL_MSDA_MAX_L || a->P < 1 || a->P > MAL_MSDA_MAX_P || a->L * a->P > MAL_MSDA_MAX_LP) return MAL_ESHAPE;
-  if (a->D < 1 || a->D > MAL_MSDA_MAX_D) return MAL_ESHAPE;
-  if (fused && a->ref_dim != 2 && a->ref_dim != 4) return MAL_ESHAPE;
+struct MsdaPlan { int vec, rows, blocks; size_t lds; };
+
+// the launch of either route for a shape, pure host code: both entry points and mal_msda_plan take their numbers from here
+static int msda_plan(int N, int S, int Lq, int M, int D, int L, int P, bool aligned, MsdaPlan* pl) {
+  if (N < 1 || S < 1 || Lq < 1 || M < 1) return MAL_ESHAPE;
+  if (L < 1 || L > MAL_MSDA_MAX_L || P < 1 || P > MAL_MSDA_MAX_P || L * P > MAL_MSDA_MAX_LP) return MAL_ESHAPE;
+  if (D < 1 || D > MAL_MSDA_MAX_D) return MAL_ESHAPE;
   // every tensor below 2^31 elements: value, output, locations
   const double lim = 2147483647.0;
-  const double md = (double)a->M * a->D;
-  if ((double)a->N * a->S * md > lim || (double)a->N * a->Lq * md > lim ||
-      (double)a->N * a->Lq * a->M * a->L * a->P * 2.0 > lim)
-    return MAL_ESHAPE;
+  const double md = (double)M * D;
+  if ((double)N * S * md > lim || (double)N * Lq * md > lim || (double)N * Lq * M * L * P * 2.0 > lim) return MAL_ESHAPE;
+  const long long total_rows = (long long)N * Lq * M;
+  pl->vec = D % 4 == 0 && aligned ? 4 : 1;
+  const int lpr = D / pl->vec;
+  const int per_row = L * P * 3 + 1;  // LDS floats of a row: locations, weights, the softmax sum
+  int rows = kMsdaThreads / lpr;
+  if (rows > kMsdaLdsFloats / per_row) rows = kMsdaLdsFloats / per_row;  // >= 42
+  if ((long long)rows > total_rows) rows = (int)total_rows;
+  pl->rows = rows;
+  pl->blocks = (int)((total_rows + rows - 1) / rows);  // (total_rows < 2^31 by the bound on the output)
+  pl->lds = (size_t)rows * per_row * sizeof(float);
+  return MAL_OK;
+}
+
+extern "C" int mal_msda_plan(int N, int S, int Lq, int M, int D, int L, int P, int aligned, int* vec, int* rows, int* blocks,
+                             size_t* lds_bytes) {
+  MsdaPlan pl;
+  const int rc = msda_plan(N, S, Lq, M, D, L, P, aligned != 0, &pl);
+  if (rc != MAL_OK) return rc;
+  if (vec) *vec = pl.vec;
+  if (rows) *rows = pl.rows;
+  if (blocks) *blocks = pl.blocks;
+  if (lds_bytes) *lds_bytes = pl.lds;
   return MAL_OK;
 }
 
 static int msda_launch(const mal_msda_args* a, bool fused) {
-  const int rc = msda_check(a, fused);
+  if (!a) return MAL_EINVAL;
+  if (!a->value || !a->spatial_shapes || !a->level_start_index || !a->sampling_locations || !a->attention_weights || !a->out)
+    return MAL_EINVAL;
+  if (fused && !a->reference_points) return MAL_EINVAL;
+  if (fused && a->ref_dim != 2 && a->ref_dim != 4) return MAL_ESHAPE;
+  MsdaPlan pl;
+  const int rc = msda_plan(a->N, a->S, a->Lq, a->M, a->D, a->L, a->P, (((uintptr_t)a->value | (uintptr_t)a->out) & 15) == 0, &pl);
   if (rc != MAL_OK) return rc;
   MsdaParams p;
   p.value = a->value; p.shapes = (const long long*)a->spatial_shapes; p.start = (const long long*)a->level_start_index;
   p.loc = a->sampling_locations; p.wgt = a->attention_weights; p.ref = a->reference_points; p.out = a->out;
   p.N = a->N; p.S = a->S; p.M = a->M; p.D = a->D; p.L = a->L; p.P = a->P; p.Lq = a->Lq; p.ref_dim = a->ref_dim;
   p.total_rows = (long long)a->N * a->Lq * a->M;
-  const bool vec4 = a->D % 4 == 0 && (((uintptr_t)a->value | (uintptr_t)a->out) & 15) == 0;
-  const int lpr = vec4 ? a->D / 4 : a->D;
-  const int per_row = a->L * a->P * 3 + 1;  // LDS floats of a row: locations, weights, the softmax sum
-  int rows = kMsdaThreads / lpr;
-  if (rows > kMsdaLdsFloats / per_row) rows = kMsdaLdsFloats / per_row;  // >= 42
-  if ((long long)rows > p.total_rows) rows = (int)p.total_rows;
-  p.rows = rows;
-  const unsigned grid = (unsigned)((p.total_rows + rows - 1) / rows);
-  const size_t lds = (size_t)rows * per_row * sizeof(float);
+  p.rows = pl.rows;
+  const bool vec4 = pl.vec == 4;
+  const unsigned grid = (unsigned)pl.blocks;
+  const size_t lds = pl.lds;
   hipStream_t st = (hipStream_t)a->stream;
   if (vec4) {
     if (fused) hipLaunchKernelGGL((msda_fwd_kernel<4, true>), dim3(grid), dim3(kMsdaThreads), lds, st, p);

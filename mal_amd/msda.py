@@ -144,6 +144,17 @@ def _launch(entry, value, spatial_shapes, level_start_index, loc, wgt, ref):
     return out
 
 
+def plan(N, S, Lq, M, D, nl, P, aligned=True):
+    """-> (channels a lane owns, rows (n, q, m) per workgroup, workgroups, dynamic LDS bytes) of either route's launch for
+    that shape (``nl`` levels), with value and out that are (``aligned``) or are not on the 16-byte grid: ``mal_msda_plan``,
+    pure host code, the function both entry points take their launch from.  A shape they refuse raises."""
+    vec, rows, blocks, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    L.check(L.load().mal_msda_plan(int(N), int(S), int(Lq), int(M), int(D), int(nl), int(P), int(bool(aligned)),
+                                   ctypes.byref(vec), ctypes.byref(rows), ctypes.byref(blocks), ctypes.byref(lds)),
+            "mal_msda_plan")
+    return vec.value, rows.value, blocks.value, lds.value
+
+
 def ms_deform_attn(value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
     """value (N,S,M,D), sampling_locations (N,Lq,M,L,P,2) in (x, y) order in [0,1] over the padded map,
     attention_weights (N,Lq,M,L,P), fp32 on the device -> (N, Lq, M*D).  ``spatial_shapes`` (L,2) rows (H_l, W_l) and

@@ -75,13 +75,25 @@ def select(scores, T):
     return order[:T]
 
 
-def checker(logits, planes, H, W, T, thing=None):
+def class_scores_fp32(logits):
+    """the fp64 softmax rounded ONCE to float32 (IEEE: to nearest even, denormals kept): what the kernel orders by"""
+    return class_scores(logits).astype(np.float32)
+
+
+def select_fp32(logits, T):
+    """the library's rule where fp64 and fp32 part ways (probabilities that underflow): the T largest in descending
+    ROUNDED score, ties by ascending flat index"""
+    return select(class_scores_fp32(logits).astype(np.float64), T)
+
+
+def checker(logits, planes, H, W, T, thing=None, fp32_rule=False):
     """one image.  logits (Q,K+1), planes (Q,h,w), thing: K-entry table or None -> dict: flat (the selected flat indices
     q*K + c after the filter, in order), query, classes, masks (n,H,W) bool, cls_score, mask_score, score (fp64),
     flat_topk (before the filter), margin_cut (relative gap between the T-th and the (T+1)-th class score, inf without a
-    (T+1)-th) and margin_sel (smallest relative gap between two selected ones)."""
+    (T+1)-th) and margin_sel (smallest relative gap between two selected ones).  ``fp32_rule``: the class scores are the
+    rounded ones of ``class_scores_fp32`` and the selection is ``select_fp32``."""
     Q, K = logits.shape[0], logits.shape[1] - 1
-    s = class_scores(logits)
+    s = class_scores_fp32(logits).astype(np.float64) if fp32_rule else class_scores(logits)
     flat_topk = select(s, T)
     ordered = np.sort(s)[::-1]
     rel = lambda a, b: abs(a - b) / max(abs(a), abs(b), 1e-300)

@@ -152,7 +152,8 @@ def load_case(tag):
     return d
 
 
-SWEEP_LEVELS = {1: ((5, 7),), 3: ((6, 9), (3, 4), (1, 1)), 4: ((7, 9), (4, 5), (2, 3), (1, 1))}
+SWEEP_LEVELS = {1: ((5, 7),), 3: ((6, 9), (3, 4), (1, 1)), 4: ((7, 9), (4, 5), (2, 3), (1, 1)),
+                8: ((7, 9), (4, 5), (2, 3), (1, 1), (1, 6), (5, 1), (3, 3), (2, 2))}  # MAL_MSDA_MAX_L levels, two of them thin
 
 
 def sweep_inputs(seed, N, Lq, M, D, L, P):
