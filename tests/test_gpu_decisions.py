@@ -396,12 +396,17 @@ def test_dualrefine_decision_exact(shape):
     """a17 (dualrefine/trainer.py:395-451,530-633; BASELINE.json configs[4] = B=8 192x640): the two (scale 0, deq_iter)
     passes run through mal_pass_fused; their decisions are exported (mal_decisions_next_pass) and forced on the oracle's
     restatement of the same lines -- every leaf then agrees at 1e-4 / the fp32 oracle's own distance from exact."""
-    from mal_amd import dualrefine, layers, ops
     from mal_amd.synthetic import make_batch
-    from oracle import aten_restated as AR
     B, H, W = shape
+    check_dualrefine_decision_exact(make_batch(B, H, W, seed=321))
+
+
+def check_dualrefine_decision_exact(batch):
+    """the body of test_dualrefine_decision_exact on a batch of the caller's"""
+    from mal_amd import dualrefine, layers, ops
+    from oracle import aten_restated as AR
+    B, _, H, W = batch["color0"].shape
     N = B * H * W
-    batch = make_batch(B, H, W, seed=321)
     torch.manual_seed(5)
     noises = [torch.randn(B, 1, H, W) for _ in range(2)]
     kw = dict(height=H, width=W, batch_size=B, n_losses=1)
@@ -523,18 +528,30 @@ def test_dualrefine_one_call_step_equals_the_operator_route(shape, kw_extra):
     per direction) against generate_images_pred + compute_losses of the same class -- the route the decision-exact test
     above pins to the oracle: same kernels underneath, so losses at 2e-6 and every gradient at 2e-5 of its scale, incl. the
     upstream quirk that the running loss enters the total once per iteration (iteration it weighs n - it)."""
-    from mal_amd import dualrefine, layers
     from mal_amd.synthetic import make_batch
     B, H, W = shape
-    batch = make_batch(B, H, W, seed=322)
+    check_dualrefine_step_equals_the_operator_route(make_batch(B, H, W, seed=322), kw_extra)
+
+
+def check_dualrefine_step_equals_the_operator_route(batch, kw_extra, pose_update=False):
+    """the body of test_dualrefine_one_call_step_equals_the_operator_route on a batch of the caller's.  ``pose_update``: with the
+    pose-update term on both routes (a refined pose of its own, _dr_build_pu); the operator route takes that term through
+    materialised candidates and other kernels, so the two are then held as
+    test_dualrefine_pose_update_one_call_against_the_operator_route_and_the_reference_fixture holds them."""
+    from mal_amd import dualrefine, layers
+    B, _, H, W = batch["color0"].shape
+    N = B * H * W
     kw = dict(height=H, width=W, batch_size=B, n_losses=1)
     kw.update(kw_extra)
     n = kw["n_losses"] + 1
     torch.manual_seed(7)
     noises = [torch.randn(B, 1, H, W).to("cuda:0") for _ in range(n)]
+    nz_pose = torch.randn(B, 1, H, W).to("cuda:0") if pose_update else None
+    if pose_update:
+        kw["disable_pose_updates"] = False
     res = {}
     for route in ("ops", "step"):
-        inputs, outputs, gl = _dr_build(batch, "cuda:0", layers.transformation_from_parameters)
+        inputs, outputs, gl = (_dr_build_pu if pose_update else _dr_build)(batch, "cuda:0", layers.transformation_from_parameters)
         for it in range(2, n):  # further iterations: their own disparity leaves
             gl["disp_it%d" % it] = (0.5 * gl["disp_teacher"].detach() + 0.5 * gl["disp_student"].detach()).clone().requires_grad_(True)
             outputs[("disp", 0, it)] = gl["disp_it%d" % it]
@@ -542,13 +559,26 @@ def test_dualrefine_one_call_step_equals_the_operator_route(shape, kw_extra):
         if route == "ops":
             lp.generate_images_pred(inputs, outputs)
             got = lp.compute_losses(inputs, outputs, noises=noises)
+            if pose_update:
+                lp.pose_update_generate_images_pred(inputs, outputs)
+                for k, v in lp.compute_pose_update_losses(inputs, outputs, noise=nz_pose).items():
+                    got[k] = got[k] + v if k in got else v
         else:
-            got = lp.loss_step(inputs, outputs, noises=noises)
+            got = lp.loss_step(inputs, outputs, noises=noises, **({"pose_noise": nz_pose} if pose_update else {}))
         got["loss"].backward()
         torch.cuda.synchronize()
         res[route] = ({k: float(v.detach()) for k, v in got.items()},
                       {k: (t.grad if t.grad is not None else torch.zeros_like(t)).cpu().numpy() for k, t in gl.items()})
     assert set(res["ops"][0]) == set(res["step"][0]), (sorted(res["ops"][0]), sorted(res["step"][0]))
+    if pose_update:
+        for k, v in res["ops"][0].items():
+            assert abs(res["step"][0][k] - v) <= 2e-5 * abs(v) + 4.0 / N, (k, res["step"][0][k], v)
+        for k, g in res["ops"][1].items():  # materialised candidates, ATen's summation order inside SSIM: all but near-tie pixels
+            o = res["step"][1][k]
+            if g.ndim == 4:
+                bad = (np.abs(g - o) > 3e-4 * np.abs(o).max()).mean()
+                assert bad <= max(2e-3, 40.0 / g.size), (k, "operator route", bad)
+        return
     for k, v in res["ops"][0].items():
         assert abs(res["step"][0][k] - v) <= 2e-6 * max(abs(v), 1e-3), (k, res["step"][0][k], v)
     for k, g in res["ops"][1].items():
@@ -727,13 +757,18 @@ def test_dualrefine_pose_update_losses_in_the_one_call_step(shape, kw_extra):
     those lines: the pass exports its decisions, they differ from the free-running oracle's at a handful of near-tie pixels,
     and with the oracle taking them every loss agrees at 2e-5 and every gradient -- the leaves collect the main loops' and the
     pose-update term's -- within max(1e-4, 1.25 x the fp32 oracle's own distance from fp64)."""
-    from mal_amd import dualrefine, layers
     from mal_amd.synthetic import make_batch
+    B, H, W = shape
+    check_dualrefine_pose_update_step(make_batch(B, H, W, seed=324), kw_extra)
+
+
+def check_dualrefine_pose_update_step(batch, kw_extra):
+    """the body of test_dualrefine_pose_update_losses_in_the_one_call_step on a batch of the caller's"""
+    from mal_amd import dualrefine, layers
     from oracle import aten_restated as AR
     from oracle import mal_oracle as O
-    B, H, W = shape
+    B, _, H, W = batch["color0"].shape
     N = B * H * W
-    batch = make_batch(B, H, W, seed=324)
     kw = dict(height=H, width=W, batch_size=B, n_losses=1)
     kw.update(kw_extra)
     torch.manual_seed(12)

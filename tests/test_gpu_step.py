@@ -102,7 +102,7 @@ def _check_step(b, kw, n0, n1):
     reference's own distance from exact arithmetic with the decisions forced.  No percent-level allowance anywhere."""
     from tests.test_gpu_decisions import check_step_decision_exact
     B, _, H, W = b["color0"].shape
-    (h, o), _, _ = check_step_decision_exact(b, kw, n0, n1, return_runs=True)
+    (h, o), counts, report = check_step_decision_exact(b, kw, n0, n1, return_runs=True)
     N = B * H * W
     amb_distil = HH.near_tie(np.concatenate([m for m in (o["mono_reproj"], o["ens"], o["multi_cands"].min(1, keepdims=True))
                                              if m is not None], 1), 2e-4)
@@ -122,6 +122,7 @@ def _check_step(b, kw, n0, n1):
     if o["ens"] is not None:
         assert np.abs(h["maps"]["ens_reproj"].numpy() - o["ens"]).max() <= 1e-4
     assert (h["maps"]["consistency_mask"].numpy() != o["consistency_mask"]).mean() <= 1e-5
+    return counts, report
 
 
 @pytest.mark.parametrize("tag", CASES + ["step_b2_32x64_temporal", "step_b2_32x64_temporal_main", G.BIG_CASE])
@@ -133,7 +134,12 @@ def test_loss_step_equals_operator_route(tag):
     b = G.batch_from_golden(z)
     B, _, H, W = b["color0"].shape
     n0, n1 = G.noises(z, (B, 1, H, W))
-    kw = G.opt_kwargs(z)
+    check_step_equals_operator_route(b, G.opt_kwargs(z), n0, n1, z)
+
+
+def check_step_equals_operator_route(b, kw, n0, n1, z=None):
+    """the comparison of test_loss_step_equals_operator_route on a batch of the caller's (``z``: the golden file of a
+    --learn_ens batch, which holds the reference's gradient of the ensemble head's disparity)"""
     if "syn_rects" in b:
         from tests.test_gpu_decisions import run_step_with_decisions
         a = run_step_with_decisions(b, kw, n0)
