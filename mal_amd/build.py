@@ -37,6 +37,16 @@ if os.environ.get("MAL_EXPERIMENTS", "0") not in ("", "0"):
     FLAGS = FLAGS + ["-DMAL_EXPERIMENTS"]
     SOURCES = SOURCES + EXPERIMENT_SOURCES
     HEADERS = HEADERS + EXPERIMENT_INCLUDES
+# Every build-time switch the sources under csrc/ test (tests/test_host_logic.py holds the two in step);
+# scripts/build_variant.py refuses any other -DMAL_*.  A/B switches whose verdict is in do not live here: the winner
+# stays as plain code and LABBOOK.md names the commit that still has the loser.
+BUILD_SWITCHES = {
+    "MAL_EXPERIMENTS": "compile the formulations of csrc/experiments/ and their options (MAL_EXPERIMENTS=1 in the environment adds their sources)",
+    "MAL_STAGE_MARKS": "instrument: stage boundaries of the row loop as labelled comments in the listing (scripts/valu_budget.py)",
+    "MAL_STAGE_TIMERS": "instrument: cycles per stage of the row loop under debug bit 64 (scripts/gpu_stage_times.py)",
+    "MAL_TEXEL_FLOATS": "constant: floats per packed texel, 3 (shipped) or 4; the Python layer asks mal_texel_floats()",
+    "MAL_EPI_G": "constant: hypotheses per wavefront of the epipolar lookup, 3 shipped (mal_epipolar.hip has the timings)",
+}
 
 
 def _hipcc():

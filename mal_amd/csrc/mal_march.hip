@@ -262,11 +262,7 @@ MAL_DEV void warp_finish(PendingWarp& pw, f2 (&x)[3], DerivRow& d) {
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
 #pragma unroll
-#if defined(MAL_SHADOW) && MAL_SHADOW
-    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(pw.t[f][k]));  // whole texels: one gather each, not 8+4 bytes (volatile: see SHADOW)
-#else
     for (int k = 0; k < 4; ++k) asm("" : "+v"(pw.t[f][k]));  // whole texels: one gather each, not 8+4 bytes
-#endif
     const texel_t A = pw.t[f][0], Bv = pw.t[f][1], C = pw.t[f][2], D = pw.t[f][3];
     const f2 a = (f2){A.x, A.y}, bb = (f2){Bv.x, Bv.y}, c = (f2){C.x, C.y}, dd = (f2){D.x, D.y};
     const float nw_ = pw.nw[f], ne_ = pw.ne[f], sw_ = pw.sw[f], se_ = pw.se[f];
@@ -302,6 +298,9 @@ MAL_DEV void warp_finish(PendingWarp& pw, f2 (&x)[3], DerivRow& d) {
 // SPEC != 0: specialisations for the passes of the whole-step lists -- packed texels on both sides, no depth map out, no
 // experiment switches (kSpecLean), and optional operands fixed at compile time, so that the operand requests, pointer
 // selects and branches those options cost in every row are compiled out (march_launch checks that a launch qualifies).
+// The values are template arguments and so part of the kernels' symbol names (build.VALU_KERNELS, profiles/): they stay.
+// kSpecConvA / kSpecConvB compile nothing out -- the convention is read per launch (compiled in it was 1 % slower than the
+// scalar branch: profiles/r04_hsum_variants_ab.txt); they record what march_launch guarantees for the launch.
 enum : int {
   kSpecLean = 1, kSpecNoDisp2 = 2,
   kSpecExtNo = 4, kSpecExtYes = 8,      // external mask: absent / present (neither: decided per launch)
@@ -310,31 +309,13 @@ enum : int {
   kSpecNoScale = 128,                   // no per-sample scale
   kSpecNoNoise = 256,                   // no tie-break noise map (the whole-step lists fold it into the identity map: Philox)
   kSpecFramed = 2048,                   // a disparity per frame (MarchParams::framed; not a LEAN specialisation)
-  kSpecConvA = 512, kSpecConvB = 1024,  // Project3D convention 0 (ManyDepth, align_corners=True) / 1 (DualRefine) known at compile time
+  kSpecConvA = 512, kSpecConvB = 1024,  // Project3D convention 0 (ManyDepth, align_corners=True) / 1 (DualRefine) guaranteed by march_launch
   kSpecTeacher = kSpecLean | kSpecNoDisp2 | kSpecExtNo | kSpecCostNo | kSpecNoScale | kSpecConvA,
   kSpecStudent = kSpecLean | kSpecNoDisp2 | kSpecExtYes | kSpecCostYes | kSpecMonoYes | kSpecConvA,      // whole-step list, scale 0
   kSpecStudentNoCost = kSpecLean | kSpecNoDisp2 | kSpecExtYes | kSpecCostNo | kSpecMonoYes | kSpecConvA, // four-scale list, scales > 0
   kSpecStudentNoEpi = kSpecLean | kSpecNoDisp2 | kSpecExtYes | kSpecCostYes | kSpecConvA,  // --temporal step: the epilogue is its own launch
   kSpecRefine = kSpecLean | kSpecNoDisp2 | kSpecCostNo | kSpecMonoYes | kSpecNoScale | kSpecConvB        // DualRefine, deq iterations > 0
 };
-// -DMAL_PROBE_W3 (scripts/w3_probe.sh; NOT a product build -- its results are wrong on purpose): what would a third wave per
-// SIMD buy the teacher's gradient pass?  The pass holds 246 VGPRs and 19.4 KB of LDS per wave; three waves need <= 168 and
-// <= 13.6 KB.  The probe compiles the SAME row loop under the 168-register cap (the compiler spills the rest to scratch) and
-// folds the ring's 24 floats per slot onto 16 (slots 16..23 alias 8..15: same LDS instructions, colliding values), and is
-// timed against the shipped kernel: if three waves WITH spill traffic are not faster than two without, no restructuring of
-// the row state that reaches 168 registers without spills can be expected to pay either.
-#ifdef MAL_PROBE_W3
-#define MAL_RI(j) ((j) < 16 ? (j) : (j) - 8)
-#define MAL_RING_POSE 16
-#define MAL_TEACHER_WAVES 3
-#else
-#define MAL_RI(j) (j)
-#define MAL_RING_POSE 24
-#define MAL_TEACHER_WAVES 2
-#endif
-#ifndef MAL_FIN_UNIFORM
-#define MAL_FIN_UNIFORM 1
-#endif
 // the parameter block as the body reads it: in the kernarg segment (constant address space, scalar loads)
 typedef __attribute__((address_space(4))) const MarchParams CMarchParams;
 // kp0: the launch's parameter block inside the kernarg segment (a merged launch holds more than one: march_pair_kernel);
@@ -351,11 +332,6 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
   constexpr bool NO_NOISE = (SPEC & kSpecNoNoise) != 0;
   constexpr bool FRAMED = (SPEC & kSpecFramed) != 0;  // frame -1 warped with disp, frame +1 with disp2; two gradient maps
   static_assert(!FRAMED || (GRAD && POSE && !NO_DISP2 && !EPI && !TEMPORAL && !EXPORT), "FRAMED: pose-gradient pass without epilogue");
-#ifdef MAL_CONV_FIXED  // A/B: Project3D's convention fixed at compile time in the specialised passes (measured 1 % SLOWER than the
-  constexpr int CONV = (SPEC & kSpecConvA) ? 0 : ((SPEC & kSpecConvB) ? 1 : -1);  // scalar branch: profiles/r04_hsum_variants_ab.txt)
-#else
-  constexpr int CONV = -1;
-#endif
   constexpr bool OUTS = EXPORT || (!GRAD && !EPI);  // the outputs the producer / the fused sweep read
   constexpr int HALO = GRAD ? 2 : 1;
   constexpr int CW = 64 - 2 * HALO;
@@ -407,17 +383,10 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
   const bool in_x = gx >= 0 && gx < W;
   const int gxr = min(max(reflect1(gx, W), 0), W - 1);
   const bool out_x = in_x && lane >= HALO && lane < 64 - HALO;
-  // adjoint of the horizontal reflection: what this lane's partials count for when they are
-  // shifted to the right neighbour (it is column 0 feeding column 1) / to the left neighbour
-#ifdef MAL_EXP_NOREFL  // experiment: what the adjoint's border multipliers cost
-  constexpr float sL = 1.0f, sR = 1.0f;
-#else
-  const float sL = gx == 0 ? 2.0f : 1.0f, sR = gx == W - 1 ? 2.0f : 1.0f;
-#endif
-  // ... the same weights as the RECEIVING lane sees them (horizontal sums through LDS, below): what arrives from the left
-  // neighbour counts twice in column 1, what arrives from the right one in column W-2
+  // adjoint of the horizontal reflection, as the RECEIVING lane sees it (horizontal sums through LDS, below): what arrives
+  // from the left neighbour (column 0 feeding column 1) counts twice in column 1, what arrives from the right one in column W-2
   const float wL = gx == 1 ? 2.0f : 1.0f, wR = gx == W - 2 ? 2.0f : 1.0f;
-  (void)sL; (void)sR; (void)wL; (void)wR;
+  (void)wL; (void)wR;
 
   // (B,1,H,W) maps are addressed as (kernel-argument pointer) + (32-bit per-lane byte offset that already holds the
   // sample's base): no 64-bit pointer arithmetic per map and row (check_shape bounds a map below 2^31 bytes)
@@ -460,43 +429,25 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
   // what the gradient row (two iterations behind the warped row) needs of its pixel -- the warped
   // values, the target and the chain-rule numbers -- waits in a 3-slot per-lane LDS ring (no bank
   // conflicts: lane-private dwords; no barrier: one wavefront) instead of ~50 registers or a re-warp
-  constexpr int RING = GRAD ? (POSE ? MAL_RING_POSE : 12) : 1;  // x, then (du, dv, u/v/rz) or e; the target row is re-read from memory
+  constexpr int RING = GRAD ? (POSE ? 24 : 12) : 1;  // x, then (du, dv, u/v/rz) or e; the target row is re-read from memory
   __shared__ float s_ring[GRAD ? 3 : 1][RING][64];
-  // Horizontal 3-sums of the gradient passes go through LDS instead of DPP (round 4; -DMAL_HSUM_DPP keeps the written-out
-  // v_add_f32_dpp blocks of round 3 for A/B).  scripts/dpp_probe.hip: at two waves per SIMD EVERY cross-lane VALU form
-  // (wave_shr, row_shr, quad_perm, v_mov_dpp, v_fmac_dpp) costs a wave 9.2 cycles of its issue timeline against 5.0 for a
-  // plain instruction, so a 3-sum by two DPP adds costs 18.4 -- and the same sum as one LDS write, two LDS reads and two
-  // plain adds 9.1 (profiles/r04_dpp_probe.txt).  A lane stores four values (16 bytes, lane stride 16: conflict-free
-  // ds_write_b128), reads its two neighbours' four (two ds_read_b128) and adds with packed instructions; 42 sums per row are
-  // 11 writes + 22 reads + 42 packed adds instead of 84 DPP adds + 18 packed multiplies (the adjoint's border weights ride
-  // on the receiving side as fused multiply-adds: x 1 or x 2 is exact, so the rounding is that of the DPP form, bit for
-  // bit).  LDS operations of a wave execute in order, so ONE 1 KB buffer serves all groups without waits in between.
-  // Lanes 0 and 63 take their own value for the missing neighbour (DPP's bound_ctrl gave 0): those are halo lanes whose sums
-  // feed only halo lanes, never an output pixel.
-  // Measured (same box, teacher pass replayed alone, profiles/r04_hsum_variants_ab.txt): LDS for the 18 partial planes -1 %,
-  // LDS for the 24 statistic planes +2 % (their results are needed at once: the LDS round trip is exposed where the DPP adds
-  // pipeline), both +2.5 %, and the gathers'-shadow ordering +7 % -- although the row loop's vector-ALU pipe cycles fall by
-  // 13 %: the pass is not bound by the vector ALU's throughput (LABBOOK.md 6).  Shipped: partial planes through LDS, the rest DPP.
-  // Build-time switches (same-box A/B with scripts/build_variant.py):
-  //   MAL_HSUM_H   the 24 statistic planes:  0 = DPP blocks, 1 = LDS, three groups in flight, 2 = LDS, all groups in flight
-  //   MAL_HSUM_HC  the 18 partial planes:    0 = DPP blocks, 1 = LDS, three groups in flight, 2 = LDS, all groups in flight
-  //   MAL_HSUM_FWD the forward-only passes:  0 = DPP (the compiler's peephole), 1 = LDS
-  //   MAL_SHADOW   1 = target sums / L1 term / pose re-derivation pinned between the gathers and the blend
-#ifndef MAL_HSUM_H
-#define MAL_HSUM_H 0
-#endif
-#ifndef MAL_HSUM_HC
-#define MAL_HSUM_HC 2
-#endif
-#ifndef MAL_HSUM_FWD
-#define MAL_HSUM_FWD 0
-#endif
-#ifndef MAL_SHADOW
-#define MAL_SHADOW 0
-#endif
-  constexpr int H_MODE = GRAD ? MAL_HSUM_H : (MAL_HSUM_FWD ? 2 : 0), HC_MODE = MAL_HSUM_HC;
-  constexpr bool HSUM_LDS = H_MODE != 0 || (GRAD && HC_MODE != 0);
-  __shared__ f4 s_stage[HSUM_LDS ? 64 : 1];
+  // Horizontal 3-sums of the gradient passes: the 18 partial planes (stage HC) go through LDS, the 24 statistic planes (stage
+  // H) through the written-out v_add_f32_dpp blocks of mal_pairs.h; the forward-only passes leave theirs to the compiler's
+  // DPP peephole (hsum3).  scripts/dpp_probe.hip: at two waves per SIMD EVERY cross-lane VALU form (wave_shr, row_shr,
+  // quad_perm, v_mov_dpp, v_fmac_dpp) costs a wave 9.2 cycles of its issue timeline against 5.0 for a plain instruction, so a
+  // 3-sum by two DPP adds costs 18.4 -- and the same sum as one LDS write, two LDS reads and two plain adds 9.1
+  // (profiles/r04_dpp_probe.txt).  A lane stores four values (16 bytes, lane stride 16: conflict-free ds_write_b128), reads its
+  // two neighbours' four (two ds_read_b128) and adds with packed instructions; the 18 sums of a row are 5 writes + 10 reads +
+  // 18 packed fused multiply-adds instead of 36 DPP adds + 18 packed multiplies (the adjoint's border weights ride on the
+  // receiving side: x 1 or x 2 is exact, so the rounding is that of the DPP form, bit for bit).  LDS operations of a wave
+  // execute in order, so ONE 1 KB buffer serves all groups without waits in between.  Lanes 0 and 63 take their own value for
+  // the missing neighbour (DPP's bound_ctrl gave 0): those are halo lanes whose sums feed only halo lanes, never an output pixel.
+  // Why this split (same box, teacher pass replayed alone, profiles/r04_hsum_variants_ab.txt): LDS for the partial planes with
+  // all five groups in flight -1 % (three in flight: no gain); LDS for the statistic planes +2 % (their results are needed at
+  // once: the LDS round trip is exposed where the DPP adds pipeline), both +2.5 %.
+  // Pinning the target sums, the L1 term and the pose re-derivation into the gathers' latency cost +7 % although the row loop's
+  // vector-ALU pipe cycles fell by 13 %: the pass is not bound by the vector ALU's throughput (LABBOOK.md 6).
+  __shared__ f4 s_stage[GRAD ? 64 : 1];
   const int laneL = max(lane - 1, 0), laneR = min(lane + 1, 63);
   // The exchange is a cross-lane communication through memory: lane i's store must be visible to lanes i-1 / i+1 before their
   // loads, and the loads must be done before the next group's stores reuse the cell.  The hardware gives that for free (a
@@ -509,21 +460,6 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     R = s_stage[laneR];
     __builtin_amdgcn_wave_barrier();
   };
-  auto nb2 = [&](f2 v, f2& L, f2& R) __attribute__((always_inline)) {  // a half group: the first 8 bytes of the lane's cell
-    *reinterpret_cast<f2*>(&s_stage[lane]) = v;
-    __builtin_amdgcn_wave_barrier();
-    L = *reinterpret_cast<const f2*>(&s_stage[laneL]);
-    R = *reinterpret_cast<const f2*>(&s_stage[laneR]);
-    __builtin_amdgcn_wave_barrier();
-  };
-  // SHADOW (round 4): what an iteration can do WITHOUT the texels of the row being warped is placed between the issue of the
-  // eight gathers and the blend that waits for them -- the one long memory latency of the iteration, of which round 3 covered
-  // ~25 instructions: the horizontal sums of the target row (they need only the target texel, requested one row ahead), the
-  // L1 term of the statistics row (raw values of the previous row) and, in the pose variants, the re-derivation of the point
-  // and of d u / d disp, d v / d disp of the gradient row (u, v, 1/z from the ring, the disparity of two rows ago).
-  constexpr bool SHADOW = MAL_SHADOW && H_MODE != 0 && GRAD;
-  // ... the pose re-derivation only where its seven results fit next to the rest (the temporal and epilogue variants spill)
-  constexpr bool SHADOW_POSE = SHADOW && POSE && !TEMPORAL && !EPI && !DBG;
   struct PosePrep { f2 alq, beq; float X[3]; f2 Xf0, Xf1, Xf2; };  // Xf*: the point per frame (FRAMED; scalars: an array member went to scratch)
   int it = 0;
   // One-row halo (p.bnd != nullptr, gradient passes of the whole-step list): a task warps ONE row beyond each end of its
@@ -651,11 +587,9 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     fin_cR = p.fin_coefs[0] * gg; fin_cS = p.fin_coefs[4] * gg;
     fin_inv = div_(1.0f, (float)p.fin_stats[b] + 1e-7f);
     fin_corr = (float)p.fin_stats[2 * p.B + b];
-#if MAL_FIN_UNIFORM
     // wave-uniform (the sample's scalars): keep them in scalar registers -- this instantiation sits at the 256-VGPR limit
     auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
     fin_cR = uni(fin_cR); fin_cS = uni(fin_cS); fin_inv = uni(fin_inv); fin_corr = uni(fin_corr);
-#endif
   }
   // reciprocals of the grid normalisation's divisors, once per wave (scalar registers)
   const float norm_rw = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(
@@ -719,8 +653,8 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
   // depth derivatives are re-derived
   auto pose_prep = [&](int q, int it, PosePrep& o) __attribute__((always_inline)) {
     float (*slot)[64] = s_ring[(it + 1) % 3];
-    const f2 pq_u = (f2){slot[MAL_RI(18)][lane], slot[MAL_RI(19)][lane]}, pq_v = (f2){slot[MAL_RI(20)][lane], slot[MAL_RI(21)][lane]};
-    const f2 pq_rz = (f2){slot[MAL_RI(22)][lane], slot[MAL_RI(23)][lane]};
+    const f2 pq_u = (f2){slot[18][lane], slot[19][lane]}, pq_v = (f2){slot[20][lane], slot[21][lane]};
+    const f2 pq_rz = (f2){slot[22][lane], slot[23][lane]};
     const float depth = depth_of(dv_2, p.min_disp, p.range);
     const float ddepth = -(depth * depth) * p.range;
     float ray[3], ik[9];
@@ -741,7 +675,7 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     o.beq = (c1 - pq_v * c2) * pq_rz * dd;
   };
   auto gradient_row = [&](CParams& p, int r, int it, const f2* hc, const Ahead& cur, unsigned so_q,
-                          float le_mono, const PosePrep* prep) __attribute__((always_inline)) {
+                          float le_mono) __attribute__((always_inline)) {
   // ================= stage G: output row q = c-1 = r-2 ======================================
   const int q = r - 2, c = r - 1;
   const bool own_q = q >= y_lo && q < y_hi;  // false: a boundary row of the neighbouring task (one-row halo)
@@ -753,17 +687,17 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
       float (*slot)[64] = s_ring[(it + 1) % 3];  // written two iterations ago
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        wq.x[k] = (f2){slot[MAL_RI(2 * k)][lane], slot[MAL_RI(2 * k + 1)][lane]};
+        wq.x[k] = (f2){slot[2 * k][lane], slot[2 * k + 1][lane]};
         if (POSE) {
-          dq.du[k] = (f2){slot[MAL_RI(6 + 2 * k)][lane], slot[MAL_RI(6 + 2 * k + 1)][lane]};
-          dq.dv[k] = (f2){slot[MAL_RI(12 + 2 * k)][lane], slot[MAL_RI(12 + 2 * k + 1)][lane]};
+          dq.du[k] = (f2){slot[6 + 2 * k][lane], slot[6 + 2 * k + 1][lane]};
+          dq.dv[k] = (f2){slot[12 + 2 * k][lane], slot[12 + 2 * k + 1][lane]};
         } else {
-          dq.e[k] = (f2){slot[MAL_RI(6 + 2 * k)][lane], slot[MAL_RI(6 + 2 * k + 1)][lane]};
+          dq.e[k] = (f2){slot[6 + 2 * k][lane], slot[6 + 2 * k + 1][lane]};
         }
       }
       if (POSE) {
-        pq_u = (f2){slot[MAL_RI(18)][lane], slot[MAL_RI(19)][lane]}; pq_v = (f2){slot[MAL_RI(20)][lane], slot[MAL_RI(21)][lane]};
-        pq_rz = (f2){slot[MAL_RI(22)][lane], slot[MAL_RI(23)][lane]};
+        pq_u = (f2){slot[18][lane], slot[19][lane]}; pq_v = (f2){slot[20][lane], slot[21][lane]};
+        pq_rz = (f2){slot[22][lane], slot[23][lane]};
       }
       wq.yrg = y2rg; wq.yb = y2b;  // target of row q = r-2, kept from its own iteration
     }
@@ -808,9 +742,8 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     MAL_MARK(61);  // ring read, L1 term, vertical adjoint sums, d loss / d warped colour done
     float gdisp, gdisp1 = 0.f;
     if (POSE) {
-      PosePrep here;
-      if (!prep) pose_prep(q, it, here);  // (the drain iterations; the row loop hands in what it formed in the gathers' shadow)
-      const PosePrep& pp = prep ? *prep : here;
+      PosePrep pp;
+      pose_prep(q, it, pp);
       const f2 alq = pp.alq, beq = pp.beq;
       const float (&X)[3] = pp.X;
       const f2 tu0 = g[0] * dq.du[0], tu1 = g[1] * dq.du[1], tu2 = g[2] * dq.du[2];
@@ -873,7 +806,7 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
                has_er = mp.ens_reproj != nullptr;
     WarpConsts wc;
     wc.src[0] = p.src[0]; wc.src[1] = p.src[1]; wc.packed = mp.packed; wc.debug = LEAN ? 0 : p.debug; wc.W = W; wc.H = H;
-    wc.convention = CONV >= 0 ? CONV : p.convention; wc.min_disp = p.min_disp; wc.range = p.range; wc.eps = p.eps;
+    wc.convention = p.convention; wc.min_disp = p.min_disp; wc.range = p.range; wc.eps = p.eps;
     wc.rw = norm_rw; wc.rh = norm_rh;
     wc.dbg = DBG ? p.dbg : nullptr; wc.dbg_n = (unsigned)(p.B * HW);
     wc.dbg_off = 0; wc.dbg_on = false;
@@ -909,41 +842,10 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
       load_cam(cam_b, P, ik);
       // the next iteration's operands go out between the projection and the gathers (measured: behind the
       // gathers is 5 % slower even when the blend then waits for the gathers only)
-#ifdef MAL_TAPS_INT  // A/B: integer tap offsets (round 3) in the specialised passes too
-      warp_issue<GRAD, POSE, DBG, false>(wc, P, ik, b, gyr, gxr, dv_, pw, [&]() { request(mp, r + 1, nxt); });
-#else
       warp_issue<GRAD, POSE, DBG, LEAN && !DBG, FRAMED>(wc, P, ik, b, gyr, gxr, dv_, pw, [&]() { request(mp, r + 1, nxt); }, dw_);
-#endif
     }
     __builtin_amdgcn_s_setprio(0);
     tick(1); MAL_MARK(1);  // small loads, prefetch, projection, gathers issued
-    // ---- in the shadow of the gathers (see SHADOW above)
-    f2 sh_hy[2] = {bc(0.f), bc(0.f)}, sh_l15 = bc(0.f);
-    float sh_hz[2] = {0.f, 0.f};
-    PosePrep prep;
-    if (SHADOW) {
-      f4 L4, R4;
-      f2 L2, R2;
-      const f2 yy = w0.yrg * w0.yrg;
-      const float yb2 = w0.yb * w0.yb;
-      nb4((f4){w0.yrg.x, w0.yrg.y, yy.x, yy.y}, L4, R4);
-      nb2((f2){w0.yb, yb2}, L2, R2);
-      if (SHADOW_POSE) pose_prep(r - 2, it, prep);
-      // L1 term of the statistics row c = r-1 (its raw values are the previous iteration's)
-      const f2 l0 = w1.yrg - w1.x[0], l1 = w1.yrg - w1.x[1], l2 = bc(w1.yb) - w1.x[2];
-      const f2 lsum = (f2){(fabsf(l0.x) + fabsf(l0.y)) + fabsf(l2.x), (fabsf(l1.x) + fabsf(l1.y)) + fabsf(l2.y)};
-      sh_l15 = bc(0.15f) * div3_2(lsum);
-      sh_hy[0] = ((f2){L4.x, L4.y} + w0.yrg) + (f2){R4.x, R4.y};
-      sh_hy[1] = ((f2){L4.z, L4.w} + yy) + (f2){R4.z, R4.w};
-      sh_hz[0] = (L2.x + w0.yb) + R2.x;
-      sh_hz[1] = (L2.y + yb2) + R2.y;
-      // keep it there: the scheduler prices a gather like any load and pulls the blend (and its wait) up in front of this
-      // block.  Two ordered (volatile) empty asm statements pin the order by data flow: this one consumes what the block
-      // computed, the ones that open the blend (warp_finish) produce the texels it reads.
-      asm volatile("" : "+v"(sh_hy[0]), "+v"(sh_hy[1]), "+v"(sh_hz[0]), "+v"(sh_hz[1]), "+v"(sh_l15));
-      if (SHADOW_POSE)
-        asm volatile("" : "+v"(prep.alq), "+v"(prep.beq), "+v"(prep.X[0]), "+v"(prep.X[1]), "+v"(prep.X[2]));
-    }
     auto finish_warp = [&]() {
       DerivRow d0;
       warp_finish<GRAD, POSE>(pw, w0.x, d0);
@@ -951,17 +853,17 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
         float (*slot)[64] = s_ring[it % 3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          slot[MAL_RI(2 * k)][lane] = w0.x[k].x; slot[MAL_RI(2 * k + 1)][lane] = w0.x[k].y;
+          slot[2 * k][lane] = w0.x[k].x; slot[2 * k + 1][lane] = w0.x[k].y;
           if (POSE) {
-            slot[MAL_RI(6 + 2 * k)][lane] = d0.du[k].x; slot[MAL_RI(6 + 2 * k + 1)][lane] = d0.du[k].y;
-            slot[MAL_RI(12 + 2 * k)][lane] = d0.dv[k].x; slot[MAL_RI(12 + 2 * k + 1)][lane] = d0.dv[k].y;
+            slot[6 + 2 * k][lane] = d0.du[k].x; slot[6 + 2 * k + 1][lane] = d0.du[k].y;
+            slot[12 + 2 * k][lane] = d0.dv[k].x; slot[12 + 2 * k + 1][lane] = d0.dv[k].y;
           } else {
-            slot[MAL_RI(6 + 2 * k)][lane] = d0.e[k].x; slot[MAL_RI(6 + 2 * k + 1)][lane] = d0.e[k].y;
+            slot[6 + 2 * k][lane] = d0.e[k].x; slot[6 + 2 * k + 1][lane] = d0.e[k].y;
           }
         }
         if (POSE) {
-          slot[MAL_RI(18)][lane] = pw.u.x; slot[MAL_RI(19)][lane] = pw.u.y; slot[MAL_RI(20)][lane] = pw.v.x; slot[MAL_RI(21)][lane] = pw.v.y;
-          slot[MAL_RI(22)][lane] = pw.rz.x; slot[MAL_RI(23)][lane] = pw.rz.y;
+          slot[18][lane] = pw.u.x; slot[19][lane] = pw.u.y; slot[20][lane] = pw.v.x; slot[21][lane] = pw.v.y;
+          slot[22][lane] = pw.rz.x; slot[23][lane] = pw.rz.y;
         }
       }
     };
@@ -995,7 +897,7 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     // ================= stage H: horizontal 3-sums of row r ====================================
     f2 h[9], hy[2];
     float hz[2];
-    if (GRAD || H_MODE != 0) {  // 24 values through LDS or three written-out blocks of DPP adds (mal_pairs.h)
+    if (GRAD) {  // 24 values through three written-out blocks of DPP adds (mal_pairs.h)
       f2 in[12];
       in[0] = w0.yrg; in[1] = w0.yrg * w0.yrg; in[2] = (f2){w0.yb, w0.yb * w0.yb};
 #pragma unroll
@@ -1004,37 +906,6 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
         in[3 + k * 3 + 0] = x; in[3 + k * 3 + 1] = x * x; in[3 + k * 3 + 2] = x * y;
       }
       f2 out[12];
-      if (SHADOW) {
-        out[0] = sh_hy[0]; out[1] = sh_hy[1]; out[2] = (f2){sh_hz[0], sh_hz[1]};
-        f4 L[4], R[4];
-        f2 L2, R2;
-        // the candidates' planes: x, x^2, x*y of the three colour pairs (18 values: four groups and a half)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) nb4((f4){in[3 + 2 * g].x, in[3 + 2 * g].y, in[4 + 2 * g].x, in[4 + 2 * g].y}, L[g], R[g]);
-        nb2(in[11], L2, R2);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          out[3 + 2 * g] = ((f2){L[g].x, L[g].y} + in[3 + 2 * g]) + (f2){R[g].x, R[g].y};
-          out[4 + 2 * g] = ((f2){L[g].z, L[g].w} + in[4 + 2 * g]) + (f2){R[g].z, R[g].w};
-        }
-        out[11] = (L2 + in[11]) + R2;
-      } else if (H_MODE != 0) {
-        // H_MODE 1: three groups in flight at a time (24 registers of neighbours; all six at once spill the pose variants)
-        constexpr int NG = H_MODE == 1 ? 3 : 6;
-#pragma unroll
-        for (int h0 = 0; h0 < 6; h0 += NG) {
-          f4 L[NG], R[NG];
-#pragma unroll
-          for (int g = 0; g < NG; ++g)
-            nb4((f4){in[2 * (h0 + g)].x, in[2 * (h0 + g)].y, in[2 * (h0 + g) + 1].x, in[2 * (h0 + g) + 1].y}, L[g], R[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) {  // (left + own) + right, as the DPP form
-            out[2 * (h0 + g)] = ((f2){L[g].x, L[g].y} + in[2 * (h0 + g)]) + (f2){R[g].x, R[g].y};
-            out[2 * (h0 + g) + 1] = ((f2){L[g].z, L[g].w} + in[2 * (h0 + g) + 1]) + (f2){R[g].z, R[g].w};
-          }
-          if (H_MODE == 1) __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
         float v8[8], r8[8];
@@ -1043,7 +914,6 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
         hsum3_block8(v8, r8);
 #pragma unroll
         for (int i = 0; i < 4; ++i) out[g * 4 + i] = (f2){r8[2 * i], r8[2 * i + 1]};
-      }
       }
       hy[0] = out[0]; hy[1] = out[1]; hz[0] = out[2].x; hz[1] = out[2].y;
 #pragma unroll
@@ -1085,15 +955,11 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
       }
       MAL_MARK(50);  // window sums + SSIM of six values done; L1, min, masks, coefficients follow
       const f2 ssum = (f2){(vc[0].x + vc[0].y) + vc[2].x, (vc[1].x + vc[1].y) + vc[2].y};
-      f2 l15 = sh_l15, lmean = bc(0.f);
-      if (!SHADOW) {
-        const f2 l0 = w1.yrg - w1.x[0], l1 = w1.yrg - w1.x[1], l2 = bc(w1.yb) - w1.x[2];
-        const f2 lsum = (f2){(fabsf(l0.x) + fabsf(l0.y)) + fabsf(l2.x), (fabsf(l1.x) + fabsf(l1.y)) + fabsf(l2.y)};
-        lmean = div3_2(lsum);
-        l15 = bc(0.15f) * lmean;
-      }
+      const f2 l0 = w1.yrg - w1.x[0], l1 = w1.yrg - w1.x[1], l2 = bc(w1.yb) - w1.x[2];
+      const f2 lsum = (f2){(fabsf(l0.x) + fabsf(l0.y)) + fabsf(l2.x), (fabsf(l1.x) + fabsf(l1.y)) + fabsf(l2.y)};
+      const f2 lmean = div3_2(lsum), l15 = bc(0.15f) * lmean;
       f2 rr = bc(0.85f) * div3_2(ssum) + l15;
-      if (VARIANTS && p.no_ssim) rr = lmean;  // --no_ssim: r = mean_c |t - p| (not in MAL_SHADOW builds, whose shadow code forms l15 only)
+      if (VARIANTS && p.no_ssim) rr = lmean;  // --no_ssim: r = mean_c |t - p|
       pi0.win = (rr.y < rr.x) ? 1 : 0;
       pi0.rp = pi0.win ? rr.y : rr.x;
       if (VARIANTS && p.avg) { pi0.win = 2; pi0.rp = (rr.x + rr.y) * 0.5f; }  // winner "2": both candidates, half each
@@ -1166,40 +1032,27 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
     if (GRAD) {
       // ================= stage HC: horizontal sums of the partial planes of row c ==============
       f2 hc[9];
-      if (HC_MODE != 0) {
-        // (w_left * left + own) + w_right * right: the border weights of the adjoint on the receiving side, fused (exact products)
-        constexpr int NG = HC_MODE == 1 ? 3 : 5;
+      // (w_left * left + own) + w_right * right: the border weights of the adjoint on the receiving side, fused (exact products).
+      // All five groups in flight (the last one holds a single pair).  The loop over h0 runs once; it stays as written because
+      // flattening it moved branches and scalar compares in the compiler's listing (profiles/march_switches_equivalence.txt).
+      constexpr int NG = 5;
 #pragma unroll
-        for (int h0 = 0; h0 < 5; h0 += NG) {  // HC_MODE 1: groups 0-2, then 3-4 (the last one holds a single pair)
-          f4 L[NG], R[NG];
+      for (int h0 = 0; h0 < 5; h0 += NG) {
+        f4 L[NG], R[NG];
 #pragma unroll
-          for (int g = 0; g < NG && h0 + g < 5; ++g) {
-            const int a = 2 * (h0 + g);
-            nb4(a + 1 < 9 ? (f4){coef[a].x, coef[a].y, coef[a + 1].x, coef[a + 1].y} : (f4){coef[a].x, coef[a].y, 0.f, 0.f}, L[g], R[g]);
-          }
-#pragma unroll
-          for (int g = 0; g < NG && h0 + g < 5; ++g) {
-            const int a = 2 * (h0 + g);
-            hc[a] = fma2((f2){R[g].x, R[g].y}, bc(wR), fma2((f2){L[g].x, L[g].y}, bc(wL), coef[a]));
-            if (a + 1 < 9) hc[a + 1] = fma2((f2){R[g].z, R[g].w}, bc(wR), fma2((f2){L[g].z, L[g].w}, bc(wL), coef[a + 1]));
-          }
-          if (HC_MODE == 1) __builtin_amdgcn_sched_barrier(0);
+        for (int g = 0; g < NG && h0 + g < 5; ++g) {
+          const int a = 2 * (h0 + g);
+          nb4(a + 1 < 9 ? (f4){coef[a].x, coef[a].y, coef[a + 1].x, coef[a + 1].y} : (f4){coef[a].x, coef[a].y, 0.f, 0.f}, L[g], R[g]);
         }
-      } else
 #pragma unroll
-      for (int g = 0; g < 3; ++g) {  // three planes (six values) per written-out block of DPP adds
-        float l6[6], c6[6], t6[6], r6[6];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const f2 vv = coef[g * 3 + i], l = vv * bc(sL), rr = vv * bc(sR);
-          l6[2 * i] = l.x; l6[2 * i + 1] = l.y; c6[2 * i] = vv.x; c6[2 * i + 1] = vv.y; t6[2 * i] = rr.x; t6[2 * i + 1] = rr.y;
+        for (int g = 0; g < NG && h0 + g < 5; ++g) {
+          const int a = 2 * (h0 + g);
+          hc[a] = fma2((f2){R[g].x, R[g].y}, bc(wR), fma2((f2){L[g].x, L[g].y}, bc(wL), coef[a]));
+          if (a + 1 < 9) hc[a + 1] = fma2((f2){R[g].z, R[g].w}, bc(wR), fma2((f2){L[g].z, L[g].w}, bc(wL), coef[a + 1]));
         }
-        hsum3_block6(l6, c6, t6, r6);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) hc[g * 3 + i] = (f2){r6[2 * i], r6[2 * i + 1]};
       }
       MAL_MARK(60);  // horizontal sums of the 18 partial planes done
-      gradient_row(p, r, it, hc, cur, so_q, le_mono, SHADOW_POSE ? &prep : nullptr);
+      gradient_row(p, r, it, hc, cur, so_q, le_mono);
     }
 
     tick(6); MAL_MARK(6);  // partial-plane sums, gradient row
@@ -1243,7 +1096,7 @@ MAL_DEV void march_body(CMarchParams* const kp0, const int task) {
       f2 hc0[9];
 #pragma unroll
       for (int i = 0; i < 9; ++i) hc0[i] = bc(0.f);
-      gradient_row(p, r, it, hc0, cur, so_q, cur.e_mono, nullptr);
+      gradient_row(p, r, it, hc0, cur, so_q, cur.e_mono);
       y2rg = w1.yrg; y2b = w1.yb;
       pi1.rp = 0.f; pi1.w = 0.f; pi1.win = 0;
       dv_2 = dv_1;
@@ -1289,13 +1142,11 @@ __global__ __launch_bounds__(64, 2) void march_export_kernel(MarchParams p_kerna
   march_body<true, true, true, false, DBG, false, true>();
 }
 #endif
-// the teacher's gradient pass of the whole-step lists (the north-star kernel), with / without the temporal hint
-#ifndef MAL_EXP_KEEP_NOISE
-#define MAL_EXP_KEEP_NOISE 0
-#endif
+// the teacher's gradient pass of the whole-step lists (the north-star kernel), with / without the temporal hint.  Two waves
+// per SIMD: a third, bought with scratch spills under the 168-VGPR cap, ran 3.8-4.6x slower (profiles/r05_w3_probe.txt).
 template <bool TEMPORAL, bool NOISE = false>  // NOISE: a tie-break noise map is given (else it is part of the identity map)
-__global__ __launch_bounds__(64, MAL_TEACHER_WAVES) void march_teacher_kernel(MarchParams p_kernarg) {
-  march_body<true, true, true, false, false, TEMPORAL, false, kSpecTeacher | (NOISE || TEMPORAL || MAL_EXP_KEEP_NOISE ? 0 : kSpecNoNoise)>();
+__global__ __launch_bounds__(64, 2) void march_teacher_kernel(MarchParams p_kernarg) {
+  march_body<true, true, true, false, false, TEMPORAL, false, kSpecTeacher | (NOISE || TEMPORAL ? 0 : kSpecNoNoise)>();
 }
 // ... and the student's gradient pass with the consistency / distillation epilogue.  (The forward-only passes gain nothing
 // from a specialisation -- same-box: ensemble 35.17 -> 35.12 us, the pass in front of the producer 56.8 -> 58.0 us -- and
@@ -1754,11 +1605,7 @@ int march_launch(MarchParams& p, int flags, hipStream_t st) {
                      (long long)p.H * p.W * (kTexel * 4) < (1ll << 24);  // tap byte offsets are formed in fp32 there
   const bool no_maps = !p.ext_mask && !p.lowest_cost && !p.sample_scale;
   const bool conv_a = p.convention == 0, conv_b = p.convention == 1;
-#ifdef MAL_CONV_FIXED
-  const bool conv_teacher = conv_a;  // (A/B build: the convention is compiled into the specialisations)
-#else
   const bool conv_teacher = conv_a || conv_b;  // the specialised teacher pass reads the convention per launch: DualRefine's iteration 0 too
-#endif
   const bool lean = lean0 && conv_teacher && no_maps && !p.disp2;                                                // kSpecTeacher
   const bool lean_student = lean0 && conv_a && !p.disp2 && p.ext_mask && p.lowest_cost && p.mono_disp;          // kSpecStudent
   const bool lean_student_nc = lean0 && conv_a && !p.disp2 && p.ext_mask && !p.lowest_cost && p.mono_disp;      // kSpecStudentNoCost

@@ -49,7 +49,8 @@ MAL_DEV void hsum3_block8(const float (&v)[8], float (&r)[8]) {
       : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
       : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
 }
-// r[i] = (shr1(l[i]) + c[i]) + shl1(t[i]), six values (the adjoint's border weights differ per direction)
+// r[i] = (shr1(l[i]) + c[i]) + shl1(t[i]), six values (the adjoint's border weights differ per direction).  The shipped
+// marching kernels sum their partial planes through LDS; experiments/march3.inc (-DMAL_EXPERIMENTS) is this block's one caller
 MAL_DEV void hsum3_block6(const float (&l)[6], const float (&c)[6], const float (&t)[6], float (&r)[6]) {
   asm("s_nop 4\n"
       "v_add_f32_dpp %0, %6, %12" MAL_DPP_SHR1 "v_add_f32_dpp %1, %7, %13" MAL_DPP_SHR1

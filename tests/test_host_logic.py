@@ -140,6 +140,38 @@ def test_dualrefine_one_call_step_refuses_what_it_does_not_cover():
             lp.loss_step({("color", 0, 0): torch.zeros(1, 3, 8, 8)}, {})
 
 
+def test_build_switch_table_matches_the_sources():
+    """build.BUILD_SWITCHES lists exactly the MAL_* names a preprocessor conditional under mal_amd/csrc/ tests (#if, #ifdef,
+    #ifndef, #elif, defined(...)): a switch nobody documents, or a documented one no source honours any more, fails here.
+    Include guards (#ifndef X directly followed by a bare #define X) and function-like macros are not switches."""
+    from mal_amd import build
+    cond = re.compile(r"^[ \t]*#[ \t]*(ifdef|ifndef|if|elif)\b(.*)$")
+    tested = {}
+    for dirpath, _, files in os.walk(build.CSRC):
+        for f in sorted(files):
+            if not f.endswith((".hip", ".h", ".inc", ".cpp")):
+                continue
+            path = os.path.join(dirpath, f)
+            lines = open(path).read().replace("\\\n", " ").split("\n")
+            for i, line in enumerate(lines):
+                m = cond.match(line)
+                if not m:
+                    continue
+                names = re.findall(r"\bMAL_\w+", m.group(2).split("//")[0])
+                if m.group(1) == "ifndef" and len(names) == 1:
+                    following = next((l for l in lines[i + 1:] if l.strip()), "")
+                    if re.match(r"^[ \t]*#[ \t]*define[ \t]+%s[ \t]*(//.*)?$" % names[0], following):
+                        continue  # an include guard
+                for n in names:
+                    tested.setdefault(n, "%s:%d" % (os.path.relpath(path, ROOT), i + 1))
+    assert tested, "no preprocessor conditional found under %s" % build.CSRC
+    undocumented = {n: at for n, at in tested.items() if n not in build.BUILD_SWITCHES}
+    stale = sorted(set(build.BUILD_SWITCHES) - set(tested))
+    assert not undocumented, "switches tested by the sources but missing from build.BUILD_SWITCHES: %s" % undocumented
+    assert not stale, "build.BUILD_SWITCHES lists switches that no source tests: %s" % stale
+    assert all(isinstance(v, str) and v.strip() and "\n" not in v for v in build.BUILD_SWITCHES.values())
+
+
 def _can_price():
     import shutil
     from mal_amd import build
@@ -150,7 +182,8 @@ def _can_price():
 def test_valu_price_list_finds_the_row_loops():
     """build() treats the vector-ALU price list as best effort (it parses a compiler listing by mangled names); the hard
     assertion lives here: the shipped sources yield a row loop and a gradient-only loop for the north-star kernel, and the
-    hand-written DPP blocks kept for A/B (-DMAL_HSUM_DPP) open with the five wait states their hazards need (mal_pairs.h)."""
+    hand-written DPP blocks (the statistic planes' in the shipped kernels, the partial planes' in experiments/march3.inc) open
+    with the five wait states their hazards need (mal_pairs.h)."""
     from mal_amd import build
     rep = build.valu_report()
     for name in ("teacher", "teacher_temporal", "student", "ensemble"):
