@@ -809,6 +809,63 @@ int mal_msda_plan(int N, int S, int Lq, int M, int D, int L, int P, int aligned,
 int mal_msda_fwd(const mal_msda_args* args);
 int mal_msda_fused_fwd(const mal_msda_args* args);
 
+/* ---- N2b: DynamicDepth's occlusion-aware forward warp, FORWARD ONLY (upstream calls it under torch.no_grad():
+ * dynamicdepth/trainer.py:494,502,517,525 and :825,840): dynamicdepth/rigid_warp.py:534-597, whose z-buffer upstream takes
+ * from torch_sparse's CUDA-only coalesce.  All float tensors fp32 and contiguous.
+ * Stage 1 (splat): every pixel of depth (B,H,W) is cut into upscale^2 sub-points that share its depth (nearest upsampling =
+ * integer division of the sub-point's coordinates); each is back-projected with inverse(K_u) (K_u: the first two rows of K
+ * times upscale), moved by pose[q] (B,3,4), divided by max(Z, 1e-3) and projected with the unscaled K; the coordinates are
+ * TRUNCATED to a cell, and a cell keeps the largest 1/Z it receives.  A sub-point counts iff x > -1 && x < W && y > -1 &&
+ * y < H, tested in float before any conversion (coordinates in (-1, 0) belong to cell 0; NaN and +-inf count nowhere).  The
+ * z-buffer is a plane of the bit patterns of 1/Z updated with a 32-bit integer atomicMax: independent of arrival order,
+ * bitwise reproducible; 0 = empty.
+ * Stage 2 (resolve): depth_w = 1 / zbuf (0 in holes), then the inverse warp of rigid_warp.py:337-373 with the inverted pose
+ * after upstream's mat2euler -> euler2mat round trip: bilinear, zero padding, align_corners=True.  Outputs, per pose q:
+ * img_w * valid (P,B,C,H,W), depth_w * valid (P,B,H,W), valid = [zbuf != 0] * [max|coord| <= 1] (P,B,H,W), and optionally the
+ * raw z-buffer (P,B,H,W uint32 bit patterns).
+ * Composition (trainer.py:503-511, optional, per pose): with dst[q] (B,C,H,W) given, dst = 0 on all channels where mask[q]
+ * (B,H,W bytes, nullable) is 1, then PER ELEMENT dst = img_w where img_w > 0 (0 instead with MAL_FWARP_NO_REPROJ).  select
+ * (B bytes, nullable) is read on the device: dst of a sample whose byte is 0 is left untouched (the outputs are still
+ * written), which replaces upstream's host read of non_cv_aug and keeps the call capturable.
+ * The per-sample matrices (both inverses of K, the inverted pose, its Euler round trip, K pose_inv) are formed on the device
+ * in fp64 and rounded to fp32 once; the per-pixel chains are fp32 in upstream's order, no fma.
+ * One call enqueues a clear of the z-buffer and three launches on `stream`; nothing is allocated, nothing synchronises.
+ * Bounds: H, W >= 2, 1 <= upscale <= MAL_FWARP_MAX_UPSCALE, 1 <= C <= MAL_FWARP_MAX_C, 1 <= n_pose <= MAL_FWARP_MAX_POSES,
+ * 1 <= B <= 65535, every tensor below 2^31 elements; anything else is MAL_ESHAPE.  A null args or required pointer is
+ * MAL_EINVAL (checked first); both before any HIP call.  ws: mal_forward_warp_workspace_bytes (0 for a refused shape).
+ * mal_forward_warp_plan is pure host code with the same shape checks: elements a lane loads at once (1), the tile of source
+ * (splat) or target (resolve) pixels a 256-thread workgroup owns, the tiles per row and per column of one (pose, sample)
+ * plane, the workgroups of either launch and its dynamic LDS bytes (0); every output pointer is nullable.
+ * mal_inverse_warp is stage 2 alone (rigid_warp.py:337-373, Euler mode, zero padding): depth (B,H,W) and pose (B,6) =
+ * (tx, ty, tz, rx, ry, rz) are the caller's; out (B,C,H,W) is the unmasked sample, valid (B,H,W) bytes.  Its ws holds the
+ * matrices only: mal_forward_warp_workspace_bytes(B, H, W, 1) is always enough. */
+#define MAL_FWARP_MAX_POSES 4
+#define MAL_FWARP_MAX_UPSCALE 4
+#define MAL_FWARP_MAX_C 4
+#define MAL_FWARP_NO_REPROJ 1     /* flags: composition writes 0 where img_w > 0 (--no_reproj_doj) */
+typedef struct mal_fwarp_args {
+  const float* img;                         /* (B,C,H,W) */
+  const float* depth;                       /* (B,H,W) */
+  const float* K;                           /* (B,3,3) */
+  const float* pose[MAL_FWARP_MAX_POSES];   /* n_pose x (B,3,4) */
+  int B, C, H, W, upscale, n_pose, flags;
+  float* img_w;                             /* out (n_pose,B,C,H,W) */
+  float* depth_w;                           /* out (n_pose,B,H,W) */
+  float* valid;                             /* out (n_pose,B,H,W) */
+  uint32_t* zbuf;                           /* out, nullable (n_pose,B,H,W) */
+  float* dst[MAL_FWARP_MAX_POSES];          /* in/out, nullable (B,C,H,W) each */
+  const uint8_t* mask[MAL_FWARP_MAX_POSES]; /* nullable (B,H,W) each */
+  const uint8_t* select;                    /* nullable (B) */
+  void* ws; size_t ws_bytes;
+  void* stream;
+} mal_fwarp_args;
+size_t mal_forward_warp_workspace_bytes(int B, int H, int W, int n_pose);
+int mal_forward_warp_plan(int B, int C, int H, int W, int upscale, int n_pose, int* vec, int* tile_w, int* tile_h,
+                          int* tiles_x, int* tiles_y, int* blocks, size_t* lds_bytes);
+int mal_forward_warp(const mal_fwarp_args* args);
+int mal_inverse_warp(const float* img, const float* depth, const float* pose, const float* K, int B, int C, int H, int W,
+                     float* out, uint8_t* valid, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- N3: ManyDepth's cost volume as MAL's student encoder builds it (forward only; upstream runs it under
  * no_grad): manydepth/networks/resnet_encoder.py:152-233 match_features + :296-312 of the encoder's forward.
  * current_feats (B,C,h,w) and lookup_feats (B,F,C,h,w) planar as the encoder produces them, C = 64 (with option
@@ -962,8 +1019,8 @@ int mal_get_option(const char* name, int* value); /* the current value of an opt
  * thread, not on the arming one) and are taken with an atomic exchange: exactly one pass consumes an arm. */
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
 /* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
- * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args, 8 mal_instances_args, 9 mal_msda_args;
- * else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
+ * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args, 8 mal_instances_args, 9 mal_msda_args,
+ * 10 mal_fwarp_args; else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
 
 /* ---- validation metrics: manydepth/trainer.py:836-1064 (Trainer.val) + evaluate_depth.py:35-53 (compute_errors) ----------

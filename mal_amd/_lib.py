@@ -136,6 +136,10 @@ SIGNATURES = {
     "mal_msda_plan": (i32, [i32] * 8 + [C.POINTER(i32)] * 3 + [C.POINTER(sz)]),
     "mal_msda_fwd": (i32, [vp]),
     "mal_msda_fused_fwd": (i32, [vp]),
+    "mal_forward_warp_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "mal_forward_warp_plan": (i32, [i32] * 6 + [C.POINTER(i32)] * 6 + [C.POINTER(sz)]),
+    "mal_forward_warp": (i32, [vp]),
+    "mal_inverse_warp": (i32, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp, vp, vp, sz, vp]),
 }
 
 class DynItem(C.Structure):
@@ -241,6 +245,15 @@ class MsdaArgs(C.Structure):
                 [(n, i32) for n in ("N", "S", "M", "D", "L", "P", "Lq", "ref_dim")] + [("out", vp), ("stream", vp)])
 
 
+class FwarpArgs(C.Structure):
+    """mal_fwarp_args (include/mal_hip.h)."""
+    _fields_ = ([(n, vp) for n in ("img", "depth", "K")] + [("pose", vp * 4)] +
+                [(n, i32) for n in ("B", "C", "H", "W", "upscale", "n_pose", "flags")] +
+                [(n, vp) for n in ("img_w", "depth_w", "valid", "zbuf")] + [("dst", vp * 4), ("mask", vp * 4), ("select", vp),
+                 ("ws", vp), ("ws_bytes", sz), ("stream", vp)])
+
+
+FWARP_MAX_POSES, FWARP_MAX_UPSCALE, FWARP_MAX_C, FWARP_NO_REPROJ = 4, 4, 4, 1
 DR_MAX_ITERS = 4
 MATCH_MAX,MATCH_U8, MATCH_F32 = 128, 0, 1
 DR_NO_AUTOMASK, DR_NO_MOTION_MASK, DR_NOISE_PHILOX, DR_AVG, DR_NO_SSIM, DR_POSE_UPDATE = 1, 2, 4, 8, 16, 32
@@ -278,7 +291,7 @@ def load():
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
     for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs, InstancesArgs,
-                                 MsdaArgs)):
+                                 MsdaArgs, FwarpArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

@@ -31,6 +31,7 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 7: return sizeof(mal_match_args);
     case 8: return sizeof(mal_instances_args);
     case 9: return sizeof(mal_msda_args);
+    case 10: return sizeof(mal_fwarp_args);
     default: return 0;
   }
 }

@@ -467,3 +467,110 @@ def upsample_bilinear_adjoint(g_out, h, w):
     g = torch.empty((B, 1, h, w), dtype=torch.float32, device=g_out.device)
     L.check(L.load().mal_upsample_bilinear_adjoint(_p(g_out), B, h, w, H, W, _p(g), _stream()), "mal_upsample_bilinear_adjoint")
     return g
+
+
+# ------------------------------------------------------------------ DynamicDepth's forward warp (mal_fwarp.hip)
+def _u8(t, name, shape, dev):
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != dev:
+        raise L.MalError("%s: expected a tensor on %s, got %s (mal_amd has no CPU fallback)" % (name, dev, t.device))
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+        raise L.MalError("%s: expected bytes of shape %s, got %s %s" % (name, tuple(shape), t.dtype, tuple(t.shape)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _grown_workspace(dev, need):
+    """the grow-only table of `workspace`, same key; whoever held intermediates in it (a whole-step forward waiting for its
+    backward) is told by `check_workspace` that it was reused"""
+    key = (dev.index, _stream())
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=dev)
+        _WS[key] = ws
+    claim_workspace(ws)
+    return ws
+
+
+def forward_warp_plan(B, C, H, W, upscale, n_pose=1):
+    """-> dict(vec, tile_w, tile_h, tiles_x, tiles_y, blocks, lds_bytes) of mal_forward_warp's splat and resolve launches:
+    ``mal_forward_warp_plan``, pure host code with the entry point's own shape checks.  A shape it refuses raises."""
+    import ctypes
+    iv = [ctypes.c_int() for _ in range(6)]
+    lds = ctypes.c_size_t()
+    L.check(L.load().mal_forward_warp_plan(int(B), int(C), int(H), int(W), int(upscale), int(n_pose),
+                                           *[ctypes.byref(v) for v in iv], ctypes.byref(lds)), "mal_forward_warp_plan")
+    names = ("vec", "tile_w", "tile_h", "tiles_x", "tiles_y", "blocks")
+    out = {n: v.value for n, v in zip(names, iv)}
+    out["lds_bytes"] = lds.value
+    return out
+
+
+def forward_warp(img, depth, poses, K, upscale, dst=None, masks=None, select=None, no_reproj=False, want_zbuf=False):
+    """img (B,C,H,W), depth (B,H,W), poses: a list of P (B,3,4), K (B,3,3) -> img_w * valid (P,B,C,H,W), depth_w * valid
+    (P,B,H,W), valid (P,B,H,W), the raw z-buffer (P,B,H,W int32 bit patterns of 1/Z) or None.  ``dst``: None or a list of P
+    entries, each None or a contiguous (B,C,H,W) tensor composed IN PLACE (trainer.py:503-511); ``masks``: per pose None or
+    (B,H,W) bytes; ``select``: None or (B) bytes read on the device."""
+    import ctypes
+    img, depth, K = _req(img, "img"), _req(depth, "depth"), _req(K, "intrinsics")
+    poses = [_req(t, "pose") for t in poses]
+    B, C, H, W = img.shape
+    P, dev = len(poses), img.device
+    if depth.shape != (B, H, W) or K.shape != (B, 3, 3) or any(t.shape != (B, 3, 4) for t in poses):
+        raise L.MalError("forward_warp: img %s needs depth (%d,%d,%d), intrinsics (%d,3,3) and poses (%d,3,4); got %s, %s, %s"
+                         % (tuple(img.shape), B, H, W, B, B, tuple(depth.shape), tuple(K.shape), [tuple(t.shape) for t in poses]))
+    if any(t.device != dev for t in [depth, K] + poses):
+        raise L.MalError("forward_warp: the inputs are on different devices")
+    if not 1 <= P <= L.FWARP_MAX_POSES:
+        raise L.MalError("forward_warp: 1 to %d poses per call, got %d" % (L.FWARP_MAX_POSES, P))
+    dst = list(dst) if dst is not None else [None] * P
+    masks = list(masks) if masks is not None else [None] * P
+    if len(dst) != P or len(masks) != P:
+        raise L.MalError("forward_warp: dst and masks need one entry per pose")
+    for d in dst:
+        if d is not None and (not d.is_cuda or d.device != dev or d.dtype != torch.float32 or d.shape != img.shape
+                              or not d.is_contiguous()):
+            raise L.MalError("forward_warp: dst is written in place and must be a contiguous float32 %s on %s" % (tuple(img.shape), dev))
+    masks = [_u8(m, "mask", (B, H, W), dev) for m in masks]
+    select = _u8(select, "select", (B,), dev)
+    lib = L.load()
+    need = lib.mal_forward_warp_workspace_bytes(B, H, W, P)
+    with torch.cuda.device(dev):
+        ws = _grown_workspace(dev, need)
+        img_w = torch.empty((P, B, C, H, W), dtype=torch.float32, device=dev)
+        depth_w = torch.empty((P, B, H, W), dtype=torch.float32, device=dev)
+        valid = torch.empty((P, B, H, W), dtype=torch.float32, device=dev)
+        zbuf = torch.empty((P, B, H, W), dtype=torch.int32, device=dev) if want_zbuf else None
+        a = L.FwarpArgs()
+        a.img, a.depth, a.K = _p(img), _p(depth), _p(K)
+        for q in range(P):
+            a.pose[q], a.dst[q], a.mask[q] = _p(poses[q]), _p(dst[q]), _p(masks[q])
+        a.B, a.C, a.H, a.W, a.upscale, a.n_pose = B, C, H, W, int(upscale), P
+        a.flags = L.FWARP_NO_REPROJ if no_reproj else 0
+        a.img_w, a.depth_w, a.valid, a.zbuf, a.select = _p(img_w), _p(depth_w), _p(valid), _p(zbuf), _p(select)
+        a.ws, a.ws_bytes, a.stream = _p(ws), ws.numel(), _stream()
+        L.check(lib.mal_forward_warp(ctypes.byref(a)), "mal_forward_warp")
+    return img_w, depth_w, valid, zbuf
+
+
+def inverse_warp(img, depth, pose, K):
+    """rigid_warp.py:337-373 in Euler mode with zero padding: img (B,C,H,W), depth (B,H,W), pose (B,6) = (tx, ty, tz, rx, ry,
+    rz), K (B,3,3) -> the sampled image (B,C,H,W), valid_points (B,H,W) bool"""
+    img, depth, pose, K = _req(img, "img"), _req(depth, "depth"), _req(pose, "pose"), _req(K, "intrinsics")
+    B, C, H, W = img.shape
+    dev = img.device
+    if depth.shape != (B, H, W) or pose.shape != (B, 6) or K.shape != (B, 3, 3):
+        raise L.MalError("inverse_warp: img %s needs depth (%d,%d,%d), pose (%d,6) and intrinsics (%d,3,3); got %s, %s, %s"
+                         % (tuple(img.shape), B, H, W, B, B, tuple(depth.shape), tuple(pose.shape), tuple(K.shape)))
+    if any(t.device != dev for t in (depth, pose, K)):
+        raise L.MalError("inverse_warp: the inputs are on different devices")
+    lib = L.load()
+    with torch.cuda.device(dev):
+        ws = _grown_workspace(dev, lib.mal_forward_warp_workspace_bytes(B, H, W, 1))
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        L.check(lib.mal_inverse_warp(_p(img), _p(depth), _p(pose), _p(K), B, C, H, W, _p(out), _p(valid), _p(ws), ws.numel(),
+                                     _stream()), "mal_inverse_warp")
+    return out, valid.view(torch.bool)
