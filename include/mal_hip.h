@@ -881,6 +881,27 @@ int mal_cost_volume(const float* current_feats, const float* lookup_feats, const
                     int set_missing_to_max, float* cost_volume, float* missing_mask, float* masked_cost_volume,
                     float* lowest_cost, float* confidence_mask, void* stream);
 
+/* ---- DynamicDepth's occlusion-aware cost volume (forward only): dynamicdepth/networks/resnet_encoder.py:148-249
+ * match_features + :299-312 of the encoder's forward.  Everything mal_cost_volume takes (planar features only), and:
+ * lookup_images (B*F,3,H,W), the images the lookup features were taken from (required when set_1 or pool; their sum over
+ * the channels < 0.15 marks the holes the forward warp left, resized by nearest to 48x128 whatever h, w are);
+ * aug_mask (B) nullable = all zero: a sample whose value is not 0 gets no occlusion handling (read on the device);
+ * cv_min: the frames fuse by minimum, a frame's cost of 0 reads as 1 and a fused cost of exactly 1 as missing (else
+ * ManyDepth's mean over the frames that hit); set_1: occluded samples become 1.0 on every channel; else pool: they become,
+ * per channel, the maximum of 0 and the non-occluded samples of the (2 pool_r + 1)^3 window over (bin, y, x).  A cell is
+ * occluded when the bilinear sample of occ[b] > 0 at its sampling position is > pool_th (occ[b]: the image of FLAT index b,
+ * as upstream indexes it, not b*F+f).  pool_r in 0..2 (MAL_EINVAL otherwise); shapes as mal_cost_volume (MAL_ESHAPE).
+ * ws: mal_cost_volume_dyn_workspace_bytes (0 for a refused shape): the occlusion images and one byte per (b,f,d,y,x);
+ * needed only when set_1 or pool.  The call enqueues two launches (four with set_1 or pool) on `stream`; it reads nothing
+ * back, allocates nothing and does not synchronise. */
+size_t mal_cost_volume_dyn_workspace_bytes(int B, int F, int D, int h, int w);
+int mal_cost_volume_dyn(const float* current_feats, const float* lookup_feats, const float* poses, const float* K,
+                        const float* inv_K, const float* depth_bins, int B, int F, int C, int D, int h, int w, float eps,
+                        int set_missing_to_max, const float* lookup_images, int H, int W, const float* aug_mask,
+                        int cv_min, int set_1, int pool, int pool_r, float pool_th, float* cost_volume,
+                        float* missing_mask, float* masked_cost_volume, float* lowest_cost, float* confidence_mask,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ---- N4 (forward): DualRefine's epipolar correlation lookup, dualrefine/networks/depth_pose.py:433-435.
  * mal_epipolar_coords = Reprojections.depth2epipolarcoords (dualrefine/networks/utils/utils.py:180-217, --gap_factor
  * depth): depth (B,1,h,w), poses (B,16) relative poses, K (B,16) at that resolution, r = --corr_radius, L = --num_levels

@@ -61,6 +61,9 @@ SIGNATURES = {
     "mal_pose_bwd": (i32, [c_pp, c_pp, C.POINTER(i32), c_pp, i32, i32, c_pp, c_pp, vp]),
     "mal_cost_volume": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, f32, i32, c_fp, c_fp, c_fp,
                               c_fp, c_fp, vp]),
+    "mal_cost_volume_dyn_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "mal_cost_volume_dyn": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, i32, f32, i32, c_fp, i32, i32,
+                                  c_fp, i32, i32, i32, i32, f32, c_fp, c_fp, c_fp, c_fp, c_fp, vp, sz, vp]),
     "mal_dyn_workspace_bytes": (sz, [i32]),
     "mal_dyn_instance_fwd": (i32, [vp, vp, i32, c_fp, c_fp, i32, i32, i32, i32, c_fp, c_fp, vp, vp, vp, sz, vp]),
     "mal_dyn_instance_bwd": (i32, [vp, vp, i32, vp, vp, c_fp, c_fp, i32, i32, i32, c_fp, c_fp, vp]),

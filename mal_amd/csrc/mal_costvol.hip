@@ -42,8 +42,9 @@ struct TapSet { int o[4]; float w[4]; float edge; };
 
 // the reference's chain for one (pixel, depth): layers.py:163-168 (X = depth * ray), :184-199 (project),
 // grid_sample's unnormalise with zeros padding, resnet_encoder.py:199-205 (border mask on the sampling position)
-MAL_DEV TapSet taps_for(const float* P, const float* ray, float depth, float eps, int w, int h) {
-  TapSet t;
+// pix_locs of one (pixel, depth): X = depth * ray (layers.py:163-168), project and normalise (:184-199).  The one place this
+// chain is written: the feature taps below and the occlusion mask of the DynamicDepth variant sample at the same position.
+MAL_DEV void grid_position(const float* P, const float* ray, float depth, float eps, int w, int h, float& gx, float& gy) {
   const float X[3] = {depth * ray[0], depth * ray[1], depth * ray[2]};
   float c[3];
   for (int i = 0; i < 3; ++i) {
@@ -54,8 +55,15 @@ MAL_DEV TapSet taps_for(const float* P, const float* ray, float depth, float eps
   }
   const float zp = c[2] + eps;
   const float u = div_safe_(c[0], zp), v = div_safe_(c[1], zp);
+  gx = (div_(u, (float)(w - 1)) - 0.5f) * 2.0f;
+  gy = (div_(v, (float)(h - 1)) - 0.5f) * 2.0f;
+}
+
+MAL_DEV TapSet taps_for(const float* P, const float* ray, float depth, float eps, int w, int h) {
+  TapSet t;
+  float gx, gy;
+  grid_position(P, ray, depth, eps, w, h, gx, gy);
   const float wm1 = (float)(w - 1), hm1 = (float)(h - 1);
-  const float gx = (div_(u, wm1) - 0.5f) * 2.0f, gy = (div_(v, hm1) - 0.5f) * 2.0f;
   const float ix = (gx + 1.0f) * (wm1 * 0.5f), iy = (gy + 1.0f) * (hm1 * 0.5f);
   const float xv = (gx / 2.0f + 0.5f) * wm1, yv = (gy / 2.0f + 0.5f) * hm1;
   t.edge = (xv >= 2.0f && xv <= (float)(w - 2) && yv >= 2.0f && yv <= (float)(h - 2)) ? 1.0f : 0.0f;
@@ -159,6 +167,8 @@ __global__ __launch_bounds__(256) void costvol_match_kernel(CostVolParams p) {
 // slower too (0.58 ms).
 constexpr int kCvG = 6;
 
+// costvol_match_dyn_kernel below repeats this kernel's setup, tap and channel loops for DynamicDepth's variant and must equal it
+// bit for bit with its options off (tests/test_gpu_dyn_costvol.py holds that): a change here is a change there.
 __global__ __launch_bounds__(256) void costvol_match_px_kernel(CostVolParams p) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int h = p.h, w = p.w, hw = h * w;
@@ -275,6 +285,348 @@ __global__ __launch_bounds__(256) void costvol_finish_kernel(CostVolParams p) {
   }
 }
 
+// ---- DynamicDepth's occlusion-aware variant (dynamicdepth/networks/resnet_encoder.py:148-249), DESIGN.md 17 -------------
+// Four launches when set_1 or pool is on, two otherwise:
+//   costvol_occ_image_kernel  (:160) one thread per cell of the 48x128 occlusion image of every lookup image: nearest source
+//                             pixel as ATen picks it, channel sum (c0 + c1) + c2 < 0.15f, one byte.
+//   costvol_occ_mask_kernel   (:194-195) m(b,f,d,y,x): the bilinear sample (zero padding, align_corners) of occ[b] -- the
+//                             image of FLAT index b, upstream's indexing, not b*F+f -- at the cell's sampling position,
+//                             compared strictly with pool_th; one byte per cell, every pixel (the pool reads border pixels
+//                             as neighbours).  Skipped for augmented samples and missing frames, whose bytes are never read.
+//   costvol_match_dyn_kernel  options off and set_1: costvol_match_px_kernel's loop, then -- only in a wavefront that holds a
+//                             masked cell with a live border mask -- the masked cells take |1 - current| per channel.
+//   costvol_match_pool_kernel pool: an LDS tile of 8 x 32 pixels x 6 bins with a halo of r (described at the kernel); a
+//                             neighbour's sample comes from taps_for with ITS ray and bin and from tap_sample, the function
+//                             the centre uses, so the maximum is exact and does not depend on the tiling.
+//                             Frames fuse by minimum (cv_min) or by the mean over the hits, in both.
+//   costvol_finish_kernel     unchanged.
+constexpr int kOccH = 48, kOccW = 128;  // resnet_encoder.py:160: fixed, whatever the matching resolution is
+
+struct CostVolDynParams {
+  CostVolParams cv;
+  const float* images;   // (B*F,3,H,W)
+  const float* aug;      // (B) nullable: != 0 switches the occlusion handling off for the sample
+  int H, W;
+  float pool_th;
+  unsigned char* occ;    // (B*F,48,128)
+  unsigned char* m;      // (B,F,D,h,w)
+};
+
+__global__ __launch_bounds__(256) void costvol_occ_image_kernel(CostVolDynParams q) {
+  const int i = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;
+  if (i >= kOccH * kOccW) return;
+  const int oy = i / kOccW, ox = i - oy * kOccW;
+  // ATen's nearest rule: floor(dst * (float)(in / out)) clamped to in - 1
+  const int sy = min((int)floorf((float)oy * ((float)q.H / (float)kOccH)), q.H - 1);
+  const int sx = min((int)floorf((float)ox * ((float)q.W / (float)kOccW)), q.W - 1);
+  const float* im = q.images + (size_t)n * 3 * q.H * q.W + (size_t)sy * q.W + sx;
+  const size_t pl = (size_t)q.H * q.W;
+  const float s = (im[0] + im[pl]) + im[2 * pl];
+  q.occ[(size_t)n * kOccH * kOccW + i] = s < 0.15f ? 1 : 0;
+}
+
+MAL_DEV bool frame_missing(const float* T) {  // :185, in the order of the plain kernel
+  float tsum = 0.f;
+  for (int i = 0; i < 16; ++i) tsum += T[i];
+  return tsum == 0.f;
+}
+
+__global__ __launch_bounds__(256) void costvol_occ_mask_kernel(CostVolDynParams q) {
+  const CostVolParams& p = q.cv;
+  const int h = p.h, w = p.w, hw = h * w;
+  const int pix = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y, bf = blockIdx.z, b = bf / p.F;
+  if (pix >= hw) return;
+  if (q.aug && q.aug[b] != 0.f) return;
+  const float* T = p.poses + (size_t)bf * 16;
+  if (frame_missing(T)) return;
+  const int y = pix / w, x = pix - y * w;
+  float ray[3], ik[9], P[12];
+  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
+  ray_of(ik, (float)x, (float)y, ray);
+  compose_P(p.K + b * 16, T, P);
+  float gx, gy;
+  grid_position(P, ray, p.bins[d], p.eps, w, h, gx, gy);  // the position the feature taps are built from
+  // grid_sample on the 48x128 image: zeros padding, bilinear, align_corners=True
+  const float ix = ((gx + 1.0f) / 2.0f) * (float)(kOccW - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(kOccH - 1);
+  const float x0f = floorf(ix), y0f = floorf(iy);
+  const float tx = ix - x0f, ex = 1.0f - tx, ty = iy - y0f, ey = 1.0f - ty;
+  const float xc = fminf(fmaxf(x0f, -2.0f), (float)kOccW + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)kOccH + 1.0f);
+  const bool wild = !(x0f == xc && y0f == yc);  // also true for NaN: every tap outside
+  const int x0 = (int)xc, y0 = (int)yc;
+  const unsigned char* oc = q.occ + (size_t)b * kOccH * kOccW;  // occ[b], not occ[b*F+f] (:194)
+  float val = 0.f;
+  if (!wild) {
+    auto tap = [&](int yy, int xx) { return (yy >= 0 && yy < kOccH && xx >= 0 && xx < kOccW) ? (float)oc[yy * kOccW + xx] : 0.f; };
+    val = tap(y0, x0) * (ex * ey);
+    val += tap(y0, x0 + 1) * (tx * ey);
+    val += tap(y0 + 1, x0) * (ex * ty);
+    val += tap(y0 + 1, x0 + 1) * (tx * ty);
+  }
+  q.m[((size_t)bf * p.D + d) * hw + pix] = val > q.pool_th ? 1 : 0;
+}
+
+// one bilinear sample of a feature plane: the multiply and the three fmas of costvol_match_px_kernel
+MAL_DEV float tap_sample(const char* pl, const unsigned off[4], const float wt[4]) {
+  const float a = *reinterpret_cast<const float*>(pl + off[0]), bb = *reinterpret_cast<const float*>(pl + off[1]);
+  const float c = *reinterpret_cast<const float*>(pl + off[2]), d = *reinterpret_cast<const float*>(pl + off[3]);
+  float o = a * wt[0];
+  o = fma_(bb, wt[1], o);
+  o = fma_(c, wt[2], o);
+  o = fma_(d, wt[3], o);
+  return o;
+}
+
+// OCC = false: options off, the plain loop and nothing else.  OCC = true: set_1; aug_mask is read here.
+template <bool OCC, bool CVMIN>
+__global__ __launch_bounds__(256) void costvol_match_dyn_kernel(CostVolDynParams q) {
+  const CostVolParams& p = q.cv;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int h = p.h, w = p.w, hw = h * w;
+  const int pix0 = (blockIdx.x * 4 + wv) * 64, grp = blockIdx.y, b = blockIdx.z;
+  if (pix0 >= hw) return;
+  const bool live = pix0 + lane < hw;
+  const int pix = min(pix0 + lane, hw - 1);
+  const int y = pix / w, x = pix - y * w;
+  const bool inner = y >= 2 && y < h - 2 && x >= 2 && x < w - 2;
+  const int d0 = grp * kCvG;
+  float ray[3], ik[9];
+  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
+  ray_of(ik, (float)x, (float)y, ray);
+  float acc[kCvG], cnt[kCvG];
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j) { acc[j] = CVMIN ? 1.f : 0.f; cnt[j] = 0.f; }
+  const float* cf = p.cur + (size_t)b * kCvC * hw;
+  const bool occ_on = OCC && !(q.aug && q.aug[b] != 0.f);  // :192, on the device; wave-uniform
+  for (int f = 0; f < p.F; ++f) {
+    const float* T = p.poses + ((size_t)b * p.F + f) * 16;
+    if (frame_missing(T)) continue;
+    float P[12];
+    compose_P(p.K + b * 16, T, P);
+    unsigned off[kCvG][4];
+    float wt[kCvG][4], edge[kCvG], sum[kCvG];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) {
+      const TapSet t = taps_for(P, ray, p.bins[min(d0 + j, p.D - 1)], p.eps, w, h);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { off[j][k] = (unsigned)t.o[k] * 4u; wt[j][k] = t.w[k]; }
+      edge[j] = inner ? t.edge : 0.f;
+      sum[j] = 0.f;
+      any = any || edge[j] != 0.f;
+    }
+    if (__ballot(any) == 0ull) continue;  // all differences are x 0: diffs 0, which cv_min reads as 1 = no change
+    const float* lf = p.look + ((size_t)b * p.F + f) * kCvC * hw;
+    for (int ch = 0; ch < kCvC; ++ch) {
+      const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
+      const float cv = cf[(size_t)ch * hw + pix];
+#pragma unroll
+      for (int j = 0; j < kCvG; ++j) sum[j] += fabsf(tap_sample(pl, off[j], wt[j]) - cv);
+    }
+    if (OCC && occ_on) {
+      // a masked cell whose border mask is 0 keeps a difference of 0 whatever it samples
+      const unsigned char* mf = q.m + ((size_t)b * p.F + f) * p.D * hw;
+      bool need[kCvG], anyneed = false;
+#pragma unroll
+      for (int j = 0; j < kCvG; ++j) {
+        need[j] = d0 + j < p.D && edge[j] != 0.f && mf[(size_t)(d0 + j) * hw + pix] != 0;
+        anyneed = anyneed || need[j];
+      }
+      if (__ballot(anyneed) != 0ull) {  // set_1 (the pooled fill has a kernel of its own)
+        float s1 = 0.f;
+        for (int ch = 0; ch < kCvC; ++ch) s1 += fabsf(1.0f - cf[(size_t)ch * hw + pix]);
+#pragma unroll
+        for (int j = 0; j < kCvG; ++j) sum[j] = need[j] ? s1 : sum[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) {
+      const float diff = sum[j] * (1.0f / (float)kCvC) * edge[j];
+      if (CVMIN) {
+        const float dm = diff == 0.f ? 1.0f : diff;            // :226
+        acc[j] = (dm < acc[j] || dm != dm) ? dm : acc[j];      // torch.minimum
+      } else {
+        acc[j] += diff;
+        cnt[j] += diff > 0.f ? 1.0f : 0.f;
+      }
+    }
+  }
+  float* out = p.cost + (size_t)b * p.D * hw + pix;
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j)
+    if (live && d0 + j < p.D) out[(size_t)(d0 + j) * hw] = CVMIN ? (acc[j] == 1.0f ? 0.f : acc[j]) : div_(acc[j], cnt[j] + 1e-7f);
+}
+
+// The pooled fill as an LDS tile.  A workgroup owns 8 x 32 pixels (thread = pixel) and kCvG bins.  Options and frames are
+// tested workgroup-uniformly; a tile without a masked cell that carries a cost runs the plain loop.  Otherwise the tile plus a
+// halo of R in bin, y and x is spread over the threads (cell i of the haloed tile belongs to thread i mod 256): each thread
+// derives ITS cells' taps once per frame with taps_for from the cell's own ray and bin, and per channel writes their samples
+// -- tap_sample, the function of the plain loop; 0 for masked cells and for cells outside the volume, which is what they
+// contribute to a maximum that already holds the masked centre's 0 -- into one of two LDS planes; after one barrier every
+// thread takes, for each of its own cells, the plane's value (unmasked: the very sample the plain loop computes), or the
+// maximum over the (2R+1)^3 window (masked), or 0 outright when the whole window is masked (found once per frame from the
+// mask bytes).  The window maximum is taken separably -- along x, along y, along the bins: 3 (2R+1) reads instead of
+// (2R+1)^3, the same value since a maximum does not depend on the order -- through two more LDS planes and two more
+// barriers, and only in a tile that holds a masked cell with an unmasked neighbour.  The sample plane is double-buffered.
+constexpr int kPtY = 8, kPtX = 32;
+
+template <int R, bool CVMIN>
+__global__ __launch_bounds__(256) void costvol_match_pool_kernel(CostVolDynParams q) {
+  constexpr int TD = kCvG + 2 * R, TY = kPtY + 2 * R, TX = kPtX + 2 * R, NCELL = TD * TY * TX, NC = (NCELL + 255) / 256;
+  __shared__ float s_v[2][NCELL];
+  __shared__ float s_x[TD * TY * kPtX], s_y[TD * kPtY * kPtX];
+  const CostVolParams& p = q.cv;
+  const int tid = threadIdx.x, ly = tid / kPtX, lx = tid - ly * kPtX;
+  const int h = p.h, w = p.w, hw = h * w;
+  const int tiles_x = (w + kPtX - 1) / kPtX;
+  const int ty0 = (blockIdx.x / tiles_x) * kPtY, tx0 = (blockIdx.x % tiles_x) * kPtX;
+  const int grp = blockIdx.y, b = blockIdx.z, d0 = grp * kCvG;
+  const bool live = ty0 + ly < h && tx0 + lx < w;
+  const int y = min(ty0 + ly, h - 1), x = min(tx0 + lx, w - 1), pix = y * w + x;
+  const bool inner = live && y >= 2 && y < h - 2 && x >= 2 && x < w - 2;
+  float ray[3], ik[9];
+  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
+  ray_of(ik, (float)x, (float)y, ray);
+  float acc[kCvG], cnt[kCvG];
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j) { acc[j] = CVMIN ? 1.f : 0.f; cnt[j] = 0.f; }
+  const float* cf = p.cur + (size_t)b * kCvC * hw;
+  const bool occ_on = !(q.aug && q.aug[b] != 0.f);  // :192, on the device; workgroup-uniform
+  for (int f = 0; f < p.F; ++f) {
+    const float* T = p.poses + ((size_t)b * p.F + f) * 16;
+    if (frame_missing(T)) continue;  // workgroup-uniform
+    float P[12];
+    compose_P(p.K + b * 16, T, P);
+    float edge[kCvG], sum[kCvG];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) {
+      edge[j] = inner ? taps_for(P, ray, p.bins[min(d0 + j, p.D - 1)], p.eps, w, h).edge : 0.f;
+      sum[j] = 0.f;
+      any = any || edge[j] != 0.f;
+    }
+    if (__syncthreads_or(any) == 0) continue;  // every difference of the tile is x 0
+    const float* lf = p.look + ((size_t)b * p.F + f) * kCvC * hw;
+    const unsigned char* mf = q.m + ((size_t)b * p.F + f) * p.D * hw;
+    // what each own cell takes per channel: 0 its own sample, 1 the window maximum, 2 nothing but 0 (whole window masked)
+    int state[kCvG];
+    bool anyneed = false;
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) {
+      const int dc = d0 + j;
+      state[j] = 0;
+      if (occ_on && dc < p.D && edge[j] != 0.f && mf[(size_t)dc * hw + pix] != 0) {
+        bool open = false;  // an inner pixel: with R <= 2 the window stays inside the image in x and y
+#pragma unroll 1
+        for (int dn = max(dc - R, 0); dn <= min(dc + R, p.D - 1); ++dn)
+#pragma unroll 1
+          for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+            for (int dx = -R; dx <= R; ++dx) open = open || mf[(size_t)dn * hw + pix + dy * w + dx] == 0;
+        state[j] = open ? 1 : 2;
+        anyneed = true;
+      }
+    }
+    bool anyopen = false;
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) anyopen = anyopen || state[j] == 1;
+    const bool tile_need = __syncthreads_or(anyneed) != 0, tile_open = __syncthreads_or(anyopen) != 0;
+    unsigned coff[NC][4];
+    float cwt[NC][4];
+    unsigned zero = 0u;  // bit k: this thread's cell k contributes 0 (masked, outside the volume, or past the tile)
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      int cd = 0, cy = 0, cx = 0;
+      bool valid;
+      if (tile_need) {
+        const int i = tid + k * 256, ii = min(i, NCELL - 1);
+        const int dz = ii / (TY * TX), rem = ii - dz * (TY * TX), ry = rem / TX;
+        cd = d0 - R + dz; cy = ty0 - R + ry; cx = tx0 - R + (rem - ry * TX);
+        valid = i < NCELL && cd >= 0 && cd < p.D && cy >= 0 && cy < h && cx >= 0 && cx < w;
+      } else {  // the plain loop: this thread's own cells
+        cd = d0 + k; cy = y; cx = x;
+        valid = k < kCvG;
+      }
+      cd = min(max(cd, 0), p.D - 1); cy = min(max(cy, 0), h - 1); cx = min(max(cx, 0), w - 1);
+      if (tile_need && valid && mf[(size_t)cd * hw + cy * w + cx] != 0) valid = false;
+      float nray[3];
+      ray_of(ik, (float)cx, (float)cy, nray);
+      const TapSet t = taps_for(P, nray, p.bins[cd], p.eps, w, h);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { coff[k][c] = (unsigned)t.o[c] * 4u; cwt[k][c] = t.w[c]; }
+      if (!valid) zero |= 1u << k;
+    }
+    if (!tile_need) {
+      for (int ch = 0; ch < kCvC; ++ch) {
+        const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
+        const float cv = cf[(size_t)ch * hw + pix];
+#pragma unroll
+        for (int j = 0; j < kCvG; ++j) sum[j] += fabsf(tap_sample(pl, coff[j], cwt[j]) - cv);
+      }
+    } else {
+      for (int ch = 0; ch < kCvC; ++ch) {
+        float* buf = s_v[ch & 1];
+        const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          const int i = tid + k * 256;
+          const float v = tap_sample(pl, coff[k], cwt[k]);
+          if (i < NCELL) buf[i] = ((zero >> k) & 1u) ? 0.f : v;
+        }
+        __syncthreads();
+        if (tile_open) {  // the window maximum, separably (a maximum does not depend on the order): along x, then y, then the bins
+          for (int i = tid; i < TD * TY * kPtX; i += 256) {
+            const int row = i / kPtX, cx = i - row * kPtX;
+            const float* c0 = buf + row * TX + cx + R;
+            float v = c0[0];
+#pragma unroll
+            for (int dx = 1; dx <= R; ++dx) v = fmaxf(v, fmaxf(c0[-dx], c0[dx]));
+            s_x[i] = v;
+          }
+          __syncthreads();
+          for (int i = tid; i < TD * kPtY * kPtX; i += 256) {
+            const int dz = i / (kPtY * kPtX), rem = i - dz * (kPtY * kPtX), ry = rem / kPtX, cx = rem - ry * kPtX;
+            const float* c0 = s_x + ((dz * TY) + ry + R) * kPtX + cx;
+            float v = c0[0];
+#pragma unroll
+            for (int dy = 1; dy <= R; ++dy) v = fmaxf(v, fmaxf(c0[-dy * kPtX], c0[dy * kPtX]));
+            s_y[i] = v;
+          }
+          __syncthreads();
+        }
+        const float cv = cf[(size_t)ch * hw + pix];
+#pragma unroll
+        for (int j = 0; j < kCvG; ++j) {
+          float v = 0.f;
+          if (state[j] == 0) {
+            v = buf[((j + R) * TY + ly + R) * TX + lx + R];
+          } else if (state[j] == 1) {  // the masked centre's own 0 is in the window
+            const float* c0 = s_y + ((j + R) * kPtY + ly) * kPtX + lx;
+            v = c0[0];
+#pragma unroll
+            for (int dd = 1; dd <= R; ++dd) v = fmaxf(v, fmaxf(c0[-dd * kPtY * kPtX], c0[dd * kPtY * kPtX]));
+          }
+          sum[j] += fabsf(v - cv);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) {
+      const float diff = sum[j] * (1.0f / (float)kCvC) * edge[j];
+      if (CVMIN) {
+        const float dm = diff == 0.f ? 1.0f : diff;
+        acc[j] = (dm < acc[j] || dm != dm) ? dm : acc[j];
+      } else {
+        acc[j] += diff;
+        cnt[j] += diff > 0.f ? 1.0f : 0.f;
+      }
+    }
+  }
+  float* out = p.cost + (size_t)b * p.D * hw + pix;
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j)
+    if (live && d0 + j < p.D) out[(size_t)(d0 + j) * hw] = CVMIN ? (acc[j] == 1.0f ? 0.f : acc[j]) : div_(acc[j], cnt[j] + 1e-7f);
+}
+
 }  // namespace mal
 
 using namespace mal;
@@ -301,6 +653,68 @@ extern "C" int mal_cost_volume(const float* current_feats, const float* lookup_f
     hipLaunchKernelGGL(costvol_match_kernel, dim3((w + 3) / 4, h, B), dim3(256), 0, st, p);
   else
     hipLaunchKernelGGL(costvol_match_px_kernel, dim3((h * w + 255) / 256, (D + kCvG - 1) / kCvG, B), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(costvol_finish_kernel, dim3((B * h * w + 63) / 64), dim3(256), 0, st, p);
+  return launch_status();
+}
+
+// ---- DynamicDepth's variant: occ images (B*F*48*128 bytes, 256-aligned) then one byte per (b,f,d,y,x)
+static size_t dyn_occ_bytes(int B, int F) { return (((size_t)B * F * kOccH * kOccW) + 255) / 256 * 256; }
+
+static int dyn_shape_status(int B, int F, int C, int D, int h, int w) {
+  if (B <= 0 || F <= 0 || D <= 0 || h < 5 || w < 5) return MAL_ESHAPE;
+  if (C != kCvC || D > 256 || B > 65535 || (long long)B * F > 65535) return MAL_ESHAPE;
+  if ((double)B * D * h * w > 2.0e9 / 4 || (double)B * F * h * w * C > 2.0e9 / 4) return MAL_ESHAPE;
+  return MAL_OK;
+}
+
+extern "C" size_t mal_cost_volume_dyn_workspace_bytes(int B, int F, int D, int h, int w) {
+  if (dyn_shape_status(B, F, kCvC, D, h, w) != MAL_OK) return 0;
+  return dyn_occ_bytes(B, F) + (size_t)B * F * D * h * w;
+}
+
+extern "C" int mal_cost_volume_dyn(const float* current_feats, const float* lookup_feats, const float* poses, const float* K,
+                                   const float* inv_K, const float* depth_bins, int B, int F, int C, int D, int h, int w,
+                                   float eps, int set_missing_to_max, const float* lookup_images, int H, int W,
+                                   const float* aug_mask, int cv_min, int set_1, int pool, int pool_r, float pool_th,
+                                   float* cost_volume, float* missing_mask, float* masked_cost_volume, float* lowest_cost,
+                                   float* confidence_mask, void* ws, size_t ws_bytes, void* stream) {
+  const int st0 = dyn_shape_status(B, F, C, D, h, w);
+  if (st0 != MAL_OK) return st0;
+  if (pool_r < 0 || pool_r > 2) return MAL_EINVAL;  // --cv_pool_radius: a wider window leaves the image around inner pixels
+  if (!current_feats || !lookup_feats || !poses || !K || !inv_K || !depth_bins || !cost_volume) return MAL_EINVAL;
+  const bool occ = set_1 || pool;
+  if (occ) {
+    if (!lookup_images || !ws) return MAL_EINVAL;
+    if (H <= 0 || W <= 0 || (double)B * F * 3 * H * W > 2.0e9) return MAL_ESHAPE;
+    if (ws_bytes < mal_cost_volume_dyn_workspace_bytes(B, F, D, h, w)) return MAL_EINVAL;
+  }
+  CostVolDynParams q = {};
+  CostVolParams& p = q.cv;
+  p.cur = current_feats; p.look = lookup_feats; p.poses = poses; p.K = K; p.invK = inv_K; p.bins = depth_bins;
+  p.B = B; p.F = F; p.D = D; p.h = h; p.w = w; p.eps = eps; p.set_missing_to_max = set_missing_to_max;
+  p.cost = cost_volume; p.missing = missing_mask; p.masked = masked_cost_volume; p.lowest_cost = lowest_cost;
+  p.confidence = confidence_mask;
+  q.images = lookup_images; q.aug = aug_mask; q.H = H; q.W = W;
+  q.pool_th = pool_th;
+  q.occ = (unsigned char*)ws; q.m = occ ? (unsigned char*)ws + dyn_occ_bytes(B, F) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((h * w + 255) / 256, (D + kCvG - 1) / kCvG, B);
+  if (occ) {
+    hipLaunchKernelGGL(costvol_occ_image_kernel, dim3((kOccH * kOccW + 255) / 256, B * F), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(costvol_occ_mask_kernel, dim3((h * w + 255) / 256, D, B * F), dim3(256), 0, st, q);
+    if (pool && !set_1) {
+      const dim3 tg(((w + kPtX - 1) / kPtX) * ((h + kPtY - 1) / kPtY), (D + kCvG - 1) / kCvG, B);
+#define MAL_POOL_LAUNCH(R) \
+      if (cv_min) hipLaunchKernelGGL((costvol_match_pool_kernel<R, true>), tg, dim3(256), 0, st, q); \
+      else hipLaunchKernelGGL((costvol_match_pool_kernel<R, false>), tg, dim3(256), 0, st, q)
+      if (pool_r == 0) { MAL_POOL_LAUNCH(0); } else if (pool_r == 1) { MAL_POOL_LAUNCH(1); } else { MAL_POOL_LAUNCH(2); }
+#undef MAL_POOL_LAUNCH
+    } else if (cv_min) hipLaunchKernelGGL((costvol_match_dyn_kernel<true, true>), grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL((costvol_match_dyn_kernel<true, false>), grid, dim3(256), 0, st, q);
+  } else {
+    if (cv_min) hipLaunchKernelGGL((costvol_match_dyn_kernel<false, true>), grid, dim3(256), 0, st, q);
+    else hipLaunchKernelGGL((costvol_match_dyn_kernel<false, false>), grid, dim3(256), 0, st, q);
+  }
   hipLaunchKernelGGL(costvol_finish_kernel, dim3((B * h * w + 63) / 64), dim3(256), 0, st, p);
   return launch_status();
 }

@@ -255,6 +255,35 @@ class ResnetEncoderMatching(_FusedGlueSwitch, nn.Module):
         return self.features, lowest_cost, confidence_mask
 
 
+class DynamicDepthEncoderMatching(ResnetEncoderMatching):
+    """dynamicdepth/networks/resnet_encoder.py:280-319: the matching encoder whose cost volume reads the holes the forward
+    warp (``mal_amd.rigid_warp.warp_dynamic_objects``) leaves in the lookup images and fills the occluded samples
+    (``mal_amd.costvol.cost_volume_outputs_dynamic``).  Same parameters and state-dict keys as its parent; ``forward`` has
+    upstream's signature and defaults, ``teacher_depth``, ``mask_noise`` and ``doj_mask`` being accepted and, as upstream,
+    never read."""
+
+    def forward(self, current_image, lookup_images, poses, K, invK, min_depth_bin=None, max_depth_bin=None,
+                teacher_depth=None, mask_noise=False, doj_mask=None, cv_min=True, aug_mask=None, set_1=False, pool=False,
+                pool_r=2, pool_th=0.4):
+        self.features = self.feature_extraction(current_image, return_all_feats=True)
+        current_feats = self.features[-1]
+        with torch.no_grad():
+            if self.adaptive_bins:
+                self.compute_depth_bins(min_depth_bin, max_depth_bin)
+            B, Fr, C3, H, W = lookup_images.shape
+            lookup_images = lookup_images.reshape(B * Fr, C3, H, W)
+            lookup_feats = self.feature_extraction(lookup_images)
+            lookup_feats = lookup_feats.reshape(B, Fr, *lookup_feats.shape[1:])
+            cost_volume, lowest_cost, confidence_mask = costvol.cost_volume_outputs_dynamic(
+                current_feats, lookup_feats, poses, K, invK, lookup_images, self.depth_bins, cv_min=cv_min, aug_mask=aug_mask,
+                set_1=set_1, pool=pool, pool_r=pool_r, pool_th=pool_th, set_missing_to_max=self.set_missing_to_max)
+        post_matching_feats = self.reduce_conv(torch.cat([self.features[-1], cost_volume], 1))
+        self.features.append(self.layer2(post_matching_feats))
+        self.features.append(self.layer3(self.features[-1]))
+        self.features.append(self.layer4(self.features[-1]))
+        return self.features, lowest_cost, confidence_mask
+
+
 # ------------------------------------------------------------------ decoders
 class Conv3x3(nn.Module):
     """manydepth/layers.py:118-134"""
