@@ -68,8 +68,16 @@ enum {
   MAL_F_EPILOGUE = 32,  /* student epilogue: consistency + distillation terms (loss_utils.py:193-254) */
   MAL_F_DUAL_DISTIL = 64,/* --dual_distil (loss_utils.py:232-234): the idx==0 target keeps its graph */
   MAL_F_SRC_PACKED = 128,/* mal_pass_fused: src[f] are texel copies made by mal_pack_texels */
-  MAL_F_TGT_PACKED = 256 /* ... and so is target */
+  MAL_F_TGT_PACKED = 256,/* ... and so is target */
+  MAL_F_ZERO_IMG = 512, /* mal_photo_holes_*: --zero_img (dynamicdepth/trainer.py:961-965): candidate and target zeroed at the
+                           candidate's holes before r is taken; the target keeps the zeros */
+  MAL_F_SELECT = 1024   /* mal_photo_holes_*: --selec_reproj (dynamicdepth/trainer.py:1058-1064): where one candidate is a
+                           hole the other one supplies rp; where both are, rp = 0 */
 };
+
+/* choice bytes of mal_photo_holes_fwd beside the candidate indices 0 and 1 */
+#define MAL_HOLE_CHOICE_NONE 254 /* both candidates are holes under MAL_F_SELECT: rp = 0, no gradient */
+#define MAL_HOLE_CHOICE_AVG 255  /* MAL_F_AVG: rp is the mean, every candidate receives 1/n_cand */
 
 int mal_version(void);
 const char* mal_strerror(int code);
@@ -164,6 +172,46 @@ int mal_photo_fwd(const float* target, const float* const* cand, int n_cand, con
 int mal_photo_bwd(const float* target, const float* const* cand, int n_cand, const uint8_t* argmin_u8,
                   const float* weight, const float* scale, const double* sums, int B, int H, int W, int flags,
                   float* const* g_cand, void* stream);
+
+/* ---- DynamicDepth's hole-aware reprojection loss on materialised candidates (mal_holes.hip) --------
+ * dynamicdepth/trainer.py:958-975 (compute_reprojection_loss under --zero_img) and :1058-1064 (--selec_reproj), both on by
+ * default upstream.  cand[c] (B,3,H,W), c < n_cand <= 2; target (B,3,H,W) as it stands in memory.
+ *   hole test    h_c = ((P_c[0] + P_c[1]) + P_c[2]) < 0.1f per pixel (pred.sum(1) < 0.1 in ATen's order)
+ *   ZERO_IMG     U_c = h_0 | .. | h_c;  r_c = r(P_c * !h_c, target * !U_c) with the r of mal_photo_fwd: the zeroed pixels lie
+ *                inside the 3x3 windows of their neighbours.  Without the flag r_c = r(P_c, target).
+ *   reduction    rp = min_c r_c (first minimum wins) or the mean with MAL_F_AVG
+ *   SELECT       n_cand == 2: where h_0, rp = r_1; where h_1, rp = r_0 (this one overrides); where both, rp = 0
+ *   weight, sums as mal_photo_fwd (MAL_F_AUTOMASK against ident + 1e-5 * noise, ext_mask; sums[0..1], f64, device)
+ * Outputs: holes (n_cand,B,H,W) bytes 0/1 (required with either hole flag), min_reproj, choice (B,1,H,W bytes: the
+ * candidate that feeds rp, MAL_HOLE_CHOICE_AVG or MAL_HOLE_CHOICE_NONE), weight_out; each map nullable.
+ * The call does NOT write the target: mal_holes_commit, launched behind it on the same stream, applies
+ * target <- target * !U_{n_cand-1}, upstream's in-place `target[mask] = 0` (so the next call -- the identity pair, the next
+ * scale, the student -- meets the zeros).  No allocation, read-back or synchronisation: both calls can be captured.
+ * ws: mal_workspace_bytes(B,H,W).  MAL_EINVAL: a null required pointer, B < 1, H or W < 2, n_cand outside 1..2,
+ * MAL_F_SELECT with n_cand != 2, a flag other than AUTOMASK, NO_SSIM, AVG, ZERO_IMG, SELECT.
+ * One workgroup per 32x8 tile stages the zeroed pair with its halo in LDS; mal_photo_holes_plan reports the tile, the
+ * halos (forward, backward), the workgroups and the LDS bytes of both launches -- pure host code, same checks. */
+int mal_photo_holes_plan(int B, int H, int W, int* tile_w, int* tile_h, int* halo_fwd, int* halo_bwd, int* blocks,
+                         size_t* lds_fwd, size_t* lds_bwd);
+int mal_photo_holes_fwd(const float* target, const float* const* cand, int n_cand, const float* ident /*nullable*/,
+                        const float* noise /*nullable*/, const float* ext_mask /*nullable*/, int B, int H, int W,
+                        int flags, uint8_t* holes, float* min_reproj, uint8_t* choice, float* weight_out, double* sums,
+                        void* ws, size_t ws_bytes, void* stream);
+int mal_holes_commit(float* target, const uint8_t* holes, int n_cand, int B, int H, int W, void* stream);
+/* The weight of a call whose identity term did not exist yet when its rp was taken: upstream evaluates the identity pair
+ * AFTER the warped pair, on the target the warped pair zeroed (trainer.py:1025-1047), so the automask of the warped pair
+ * is formed behind both.  weight_out = [min_reproj <= ident + 1e-5 * noise] * ext_mask (each nullable, noise only with
+ * ident), sums[0] = sum(min_reproj * w), sums[1] = sum(w), as the forward forms them.  Pointwise; ws as above. */
+int mal_holes_weight(const float* min_reproj, const float* ident /*nullable*/, const float* noise /*nullable*/,
+                     const float* ext_mask /*nullable*/, int B, int H, int W, float* weight_out, double* sums, void* ws,
+                     size_t ws_bytes, void* stream);
+/* d(sum(rp*w))/d cand_c -> g_cand[c] (B,3,H,W, nullable), scaled as mal_photo_bwd.  target is the target AS THE FORWARD
+ * READ IT (a copy taken before mal_holes_commit and before any later call zeroed it further); holes, choice, weight come
+ * from the forward.  Under MAL_F_ZERO_IMG exactly zero at the h_c pixels of candidate c (the masked copy was written over),
+ * hence in both candidates where both are holes; a pixel whose choice is MAL_HOLE_CHOICE_NONE hands on no gradient. */
+int mal_photo_holes_bwd(const float* target, const float* const* cand, int n_cand, const uint8_t* holes,
+                        const uint8_t* choice, const float* weight, const float* scale, const double* sums, int B, int H,
+                        int W, int flags, float* const* g_cand, void* stream);
 
 /* ---- the fused pass: a2-a4 + a7-a10 (+ the a11 epilogue) in ONE launch ------------------
  * Replaces generate_images_pred + compute_mono_losses / compute_main_losses /

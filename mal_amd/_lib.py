@@ -45,6 +45,11 @@ SIGNATURES = {
                            c_fp, c_pp, vp, sz, vp]),
     "mal_photo_fwd": (i32, [c_fp, c_pp, i32, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp, c_fp, c_fp, c_fp, vp, sz, vp]),
     "mal_photo_bwd": (i32, [c_fp, c_pp, i32, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_pp, vp]),
+    "mal_photo_holes_plan": (i32, [i32, i32, i32] + [C.POINTER(i32)] * 5 + [C.POINTER(sz)] * 2),
+    "mal_photo_holes_fwd": (i32, [c_fp, c_pp, i32, c_fp, c_fp, c_fp, i32, i32, i32, i32, vp, c_fp, vp, c_fp, c_fp, vp, sz, vp]),
+    "mal_holes_commit": (i32, [c_fp, vp, i32, i32, i32, i32, vp]),
+    "mal_holes_weight": (i32, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, c_fp, vp, sz, vp]),
+    "mal_photo_holes_bwd": (i32, [c_fp, c_pp, i32, vp, vp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_pp, vp]),
     "mal_pass_fused": (i32, [c_fp, c_fp, c_fp, c_fp, c_pp, c_pp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32,
                              i32, f32, f32, f32, i32, i32, c_fp, c_fp, c_fp, c_fp, c_fp, c_pp, c_fp, c_fp, vp, sz, vp]),
     "mal_distil_epilogue": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp, c_fp, c_fp, c_fp,
@@ -270,6 +275,8 @@ DEC_WIN, DEC_DISTIL, DEC_SMOOTH_X, DEC_SMOOTH_Y, DEC_TAP0, DEC_TAP1, DEC_L1, DEC
 
 # flags (include/mal_hip.h)
 F_AUTOMASK, F_GRAD, F_POSE_GRAD, F_NO_SSIM, F_AVG, F_EPILOGUE, F_DUAL_DISTIL, F_SRC_PACKED, F_TGT_PACKED = 1, 2, 4, 8, 16, 32, 64, 128, 256
+F_ZERO_IMG, F_SELECT = 512, 1024  # mal_photo_holes_*
+HOLE_CHOICE_NONE, HOLE_CHOICE_AVG = 254, 255
 
 _lib = None
 

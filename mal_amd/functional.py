@@ -209,6 +209,94 @@ class PhotoLossFn(Function):
         return (None, None, None, None, None, *g)
 
 
+class HolePhotoLossFn(Function):
+    """DynamicDepth's hole-aware reprojection term on materialised candidates (dynamicdepth/trainer.py:958-975 under
+    --zero_img, :1058-1064 --selec_reproj): PhotoLossFn's shape plus the in-place target.
+
+    One call is one scale of upstream's ``compute_losses`` (:1025-1090) in upstream's order:
+      1. the warped candidates ``imgs[:-n_ident]`` against the target as it stands (mal_photo_holes_fwd), then the commit;
+      2. the identity pair ``imgs[-n_ident:]`` (never ``F_SELECT``) against the target the first call left, then its commit
+         -- evaluated when the automask needs it or when ``F_ZERO_IMG`` makes its zeroing visible to later calls;
+      3. the weight: ``automask`` compares rp of (1) with the identity minimum of (2) plus 1e-5 ``noise`` (mal_holes_weight);
+         otherwise ``ext_mask`` alone (the student's consistency_mask * (1 - augmentation_mask)), inside the first kernel.
+    -> (sum(rp*w)/(sum(w)+1e-7), min_reproj map, weight map, holes (n,B,H,W) bytes, choice bytes, target).  With ``F_ZERO_IMG`` the target
+    is zeroed IN PLACE, as upstream's ``target[mask] = 0``: it is marked dirty and handed back (the same tensor).  The
+    backward never reads the caller's target again: it keeps a copy taken before the first commit, so calls that zero the
+    target further (the identity pair, the next scale, the student's pass) do not change the gradients of this one.
+    """
+
+    @staticmethod
+    def forward(ctx, target, noise, ext_mask, flags, automask, n_ident, *imgs):
+        n_ident = int(n_ident)
+        cands, idents = imgs[:len(imgs) - n_ident], imgs[len(imgs) - n_ident:]
+        zero = bool(flags & L.F_ZERO_IMG)
+        kflags = flags & (L.F_ZERO_IMG | L.F_SELECT | L.F_AVG | L.F_NO_SSIM)
+        if automask and not idents:
+            raise L.MalError("HolePhotoLossFn: the automask compares with the identity pair; none was given")
+        seen = target
+        if zero:
+            if not target.is_contiguous():
+                raise L.MalError("HolePhotoLossFn: --zero_img writes the target in place; it must be contiguous")
+            seen = target.clone()
+        holes, mn, ch, wt, sums = ops.photo_holes_fwd(target, cands, None, None, None if automask else ext_mask, kflags)
+        if zero:
+            ops.holes_commit(target, holes)
+            ctx.mark_dirty(target)
+        if idents and (automask or zero):
+            ih, idn, _, _, _ = ops.photo_holes_fwd(target, idents, None, None, None, kflags & ~L.F_SELECT)
+            if zero:
+                ops.holes_commit(target, ih)
+            if automask:
+                wt, sums = ops.holes_weight(mn, idn, noise, ext_mask)
+        ctx.save_for_backward(seen, holes, ch, wt, sums, *cands)
+        ctx.flags, ctx.first = kflags, 6
+        ctx.set_materialize_grads(False)
+        loss = ops.finish_scalars(sums[0:1], sums[1:2], 1e-7).reshape(())
+        ctx.mark_non_differentiable(mn, wt, holes, ch, target)   # the target stays the caller's plain input tensor
+        return loss, mn, wt, holes, ch, target
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, _g_mn, _g_wt, _g_holes, _g_ch, _g_target):
+        seen, holes, ch, wt, sums = ctx.saved_tensors[:5]
+        cands = ctx.saved_tensors[5:]
+        n_in = len(ctx.needs_input_grad)
+        if g_loss is None:
+            return (None,) * n_in
+        need = [ctx.needs_input_grad[ctx.first + i] for i in range(len(cands))]
+        g = ops.photo_holes_bwd(seen, cands, holes, ch, wt, _scalar(g_loss), sums, ctx.flags, need)
+        return (None,) * ctx.first + tuple(g) + (None,) * (n_in - ctx.first - len(cands))
+
+
+class HoleReprojFn(Function):
+    """``compute_reprojection_loss(pred, target)`` of dynamicdepth/trainer.py:958-975, the single-candidate form:
+    -> (r (B,1,H,W), target).  With ``F_ZERO_IMG`` the target is zeroed in place at ``pred``'s holes (marked dirty); the
+    backward works from a copy taken before."""
+
+    @staticmethod
+    def forward(ctx, pred, target, flags):
+        kflags = flags & (L.F_ZERO_IMG | L.F_NO_SSIM)
+        zero = bool(kflags & L.F_ZERO_IMG)
+        seen = target.clone() if zero else target
+        holes, mn, ch, _, _ = ops.photo_holes_fwd(target, [pred], None, None, None, kflags)
+        if zero:
+            ops.holes_commit(target, holes)
+            ctx.mark_dirty(target)
+        ctx.save_for_backward(seen, holes, ch, pred)
+        ctx.flags = kflags
+        ctx.mark_non_differentiable(target)
+        return mn, target
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_r, _g_target):
+        seen, holes, ch, pred = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g = ops.photo_holes_bwd(seen, [pred], holes, ch, g_r.contiguous(), None, None, ctx.flags, [True])
+        return g[0], None, None
+
+
 class FusedPassFn(Function):
     """One launch of mal_pass_fused for a whole pass of manydepth/trainer.py:573-612.
 

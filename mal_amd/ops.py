@@ -305,6 +305,103 @@ def photo_bwd(target, cands, argmin, weight, scale, sums, flags, need):
     return g
 
 
+# ------------------------------------------------------------------ DynamicDepth's hole-aware loss (mal_holes.hip)
+def _hole_inputs(what, target, cands, flags):
+    cands = list(cands)
+    if not 1 <= len(cands) <= 2:
+        raise L.MalError("%s: 1 or 2 candidates per call, got %d" % (what, len(cands)))
+    if (flags & L.F_SELECT) and len(cands) != 2:
+        raise L.MalError("%s: selec_reproj (F_SELECT) chooses between exactly two candidates, got %d" % (what, len(cands)))
+    if target.dim() != 4 or target.shape[1] != 3 or target.shape[2] < 2 or target.shape[3] < 2:
+        raise L.MalError("%s: the target must be (B,3,H,W) with H, W >= 2, got %s" % (what, tuple(target.shape)))
+    for c in cands:
+        if c.shape != target.shape or c.device != target.device:
+            raise L.MalError("%s: candidate %s on %s does not match the target %s on %s"
+                             % (what, tuple(c.shape), c.device, tuple(target.shape), target.device))
+    return _req(target, "target"), [_req(c, "cand") for c in cands]
+
+
+def _hole_map(t, name, shape, dev):
+    t = _req(t, name)
+    if t is not None and (tuple(t.shape) != tuple(shape) or t.device != dev):
+        raise L.MalError("%s: expected %s on %s, got %s on %s" % (name, tuple(shape), dev, tuple(t.shape), t.device))
+    return t
+
+
+def photo_holes_plan(B, H, W):
+    """-> dict(tile_w, tile_h, halo_fwd, halo_bwd, blocks, lds_fwd, lds_bwd) of mal_photo_holes_fwd / _bwd: pure host code"""
+    import ctypes
+    iv = [ctypes.c_int() for _ in range(5)]
+    lds = [ctypes.c_size_t() for _ in range(2)]
+    L.check(L.load().mal_photo_holes_plan(int(B), int(H), int(W), *[ctypes.byref(v) for v in iv + lds]), "mal_photo_holes_plan")
+    out = {n: v.value for n, v in zip(("tile_w", "tile_h", "halo_fwd", "halo_bwd", "blocks"), iv)}
+    out["lds_fwd"], out["lds_bwd"] = lds[0].value, lds[1].value
+    return out
+
+
+def photo_holes_fwd(target, cands, ident=None, noise=None, ext_mask=None, flags=0):
+    """-> holes (n,B,H,W) uint8, min_reproj, choice (B,1,H,W uint8), weight, sums (8 f64, [0] = sum rp*w, [1] = sum w).
+    The target is READ only: ``holes_commit`` behind this call zeroes it as upstream's ``target[mask] = 0`` does."""
+    target, cands = _hole_inputs("photo_holes_fwd", target, cands, flags)
+    B, _, H, W = target.shape
+    dev = target.device
+    ident, noise, ext_mask = (_hole_map(t, n, (B, 1, H, W), dev) for t, n in ((ident, "ident"), (noise, "noise"),
+                                                                              (ext_mask, "ext_mask")))
+    if (flags & L.F_AUTOMASK) and ident is None:
+        raise L.MalError("photo_holes_fwd: F_AUTOMASK needs ident")
+    holes = torch.empty(len(cands), B, H, W, dtype=torch.uint8, device=dev)
+    mn = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+    ch = torch.empty(B, 1, H, W, dtype=torch.uint8, device=dev)
+    wt = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+    sums = torch.zeros(8, dtype=torch.float64, device=dev)
+    ws = workspace(dev, B, H, W)
+    L.check(L.load().mal_photo_holes_fwd(_p(target), L.ptr_array([_p(c) for c in cands]), len(cands), _p(ident), _p(noise),
+                                         _p(ext_mask), B, H, W, flags, _p(holes), _p(mn), _p(ch), _p(wt), _p(sums), _p(ws),
+                                         ws.numel(), _stream()), "mal_photo_holes_fwd")
+    return holes, mn, ch, wt, sums
+
+
+def holes_commit(target, holes):
+    """target (B,3,H,W), written IN PLACE: zero where any of ``holes`` (n,B,H,W) is set.  Returns ``target``."""
+    if not target.is_cuda or target.dtype != torch.float32 or not target.is_contiguous() or target.dim() != 4 or target.shape[1] != 3:
+        raise L.MalError("holes_commit: the target is written in place and must be a contiguous float32 (B,3,H,W) device tensor")
+    B, _, H, W = target.shape
+    holes = _u8(holes, "holes", (holes.shape[0], B, H, W), target.device)
+    L.check(L.load().mal_holes_commit(_p(target), _p(holes), holes.shape[0], B, H, W, _stream()), "mal_holes_commit")
+    return target
+
+
+def holes_weight(min_reproj, ident=None, noise=None, ext_mask=None):
+    """-> weight (B,1,H,W) = [min_reproj <= ident + 1e-5 noise] * ext_mask, sums (8 f64): the automask of a call whose
+    identity term was evaluated after it (mal_holes_weight)"""
+    mn = _req(min_reproj, "min_reproj")
+    B, _, H, W = mn.shape
+    dev = mn.device
+    ident, noise, ext_mask = (_hole_map(t, n, (B, 1, H, W), dev) for t, n in ((ident, "ident"), (noise, "noise"),
+                                                                              (ext_mask, "ext_mask")))
+    wt = torch.empty_like(mn)
+    sums = torch.zeros(8, dtype=torch.float64, device=dev)
+    ws = workspace(dev, B, H, W)
+    L.check(L.load().mal_holes_weight(_p(mn), _p(ident), _p(noise), _p(ext_mask), B, H, W, _p(wt), _p(sums), _p(ws), ws.numel(),
+                                      _stream()), "mal_holes_weight")
+    return wt, sums
+
+
+def photo_holes_bwd(target, cands, holes, choice, weight, scale, sums, flags, need):
+    """``target``: the target as the forward read it (a copy from before the commit), not the caller's tensor of now"""
+    target, cands = _hole_inputs("photo_holes_bwd", target, cands, flags)
+    B, _, H, W = target.shape
+    dev = target.device
+    holes = _u8(holes, "holes", (len(cands), B, H, W), dev)
+    choice = _u8(choice, "choice", (B, 1, H, W), dev)
+    weight = _hole_map(weight, "weight", (B, 1, H, W), dev)
+    g = [torch.empty_like(c) if n else None for c, n in zip(cands, need)]
+    L.check(L.load().mal_photo_holes_bwd(_p(target), L.ptr_array([_p(c) for c in cands]), len(cands), _p(holes), _p(choice),
+                                         _p(weight), _p(scale), _p(sums), B, H, W, flags & ~L.F_AUTOMASK,
+                                         L.ptr_array([_p(x) for x in g]), _stream()), "mal_photo_holes_bwd")
+    return g
+
+
 # ------------------------------------------------------------------ texel packing of the sources
 _PACKED = {}
 pack_sources = True  # fused pass gathers whole texels from (B,H,W,n) copies of the sources (n = mal_texel_floats())
