@@ -1089,14 +1089,15 @@ int mal_get_option(const char* name, int* value); /* the current value of an opt
 int mal_build_has_experiments(void); /* 1 when the library contains the -DMAL_EXPERIMENTS formulations */
 /* sizeof of the argument blocks as THIS library was compiled (0 mal_step_args, 1 mal_ms_args, 2 mal_dr_args, 3 mal_dyn_item,
  * 4 mal_step_scales_args, 5 mal_eval_seg, 6 mal_eval_args, 7 mal_match_args, 8 mal_instances_args, 9 mal_msda_args,
- * 10 mal_fwarp_args; else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
+ * 10 mal_fwarp_args, 11 mal_eval_dyn_args; else 0): a binding in another language checks its own layout against it once, at load (mal_amd/_lib.py does). */
 size_t mal_struct_bytes(int which);
 
 /* ---- validation metrics: manydepth/trainer.py:836-1064 (Trainer.val) + evaluate_depth.py:35-53 (compute_errors) ----------
  * The ground truth of a split is packed once (mal_amd/evaluate.py): per image a segment of `slots` packed points.  Sparse
  * (LiDAR) segments hold the flat index y*gt_w+x of each valid point (mask and crop applied) and its value; dense segments
  * (CityScapes windows) hold the rw-wide rectangle at (x0, y0) of the resized image row by row, with 0 where the mask is
- * false.  `gt` is f64 when gt_f64, else fp32; med_gt is np.median of the image's valid ground truth (exact, in its dtype). */
+ * false.  `gt` is f64 when gt_f64, else fp32; med_gt is np.median of the image's valid ground truth (exact, in its dtype) --
+ * or, packed for mal_eval_dyn_accumulate below, torch.median's lower middle value. */
 typedef struct mal_eval_seg {
   int64_t off;     /* first packed slot of the image */
   int slots;       /* packed slots (sparse: = n) */
@@ -1137,6 +1138,45 @@ int mal_eval_mean(const double* img_out, int n_images, double* out7, void* strea
 size_t mal_eval_errors_workspace_bytes(size_t n);
 int mal_eval_errors(const void* gt, int gt_f64, const void* pred, int pred_f64, size_t n, double* out7, void* ws,
                     size_t ws_bytes, void* stream);
+
+/* ---- DynamicDepth's validation: dynamicdepth/trainer.py:1158-1257 (compute_depth_losses), :881-886 (val's aggregation),
+ * layers.py:244-262 (compute_depth_errors) ---------------------------------------------------------------------------------
+ * The packing is the one above (mal_amd/dyn_eval.py); med_gt holds torch.median's LOWER middle value of the image's valid
+ * ground truth, and n < 2^24.  One batch: disp (B,1,H,W) sigmoid outputs and mask (B,1,mh,mw) object masks of images
+ * first .. first+B-1.  Per valid point: disp_to_depth(disp, min_depth, max_depth)[1] at the four taps (as
+ * mal_disp_to_depth), F.interpolate(mode="bilinear", align_corners=False) evaluated pointwise, clamp(1e-3, 80), and the
+ * region byte F.interpolate(mask) (nearest) != 0.  Per image: torch.median of the predictions, the ratio, the float32
+ * multiply, the second clamp, and compute_depth_errors over the valid points and over those with the region byte set.
+ * img_out[i*MAL_EVAL_DYN_ROW + ..]: 0..6 abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 over the valid points; 7..13 the same
+ * over the object region (all 0 when it is empty); 14 ratio; 15 n_all; 16 n_doj; 17 the median of the prediction.
+ * Scratch, the batch's slots (seg[first+B-1].off + slots - seg[first].off) each: pred (the clamped prediction before
+ * scaling), region (the bytes), scaled (NULL, or the prediction after scaling and the second clamp). */
+#define MAL_EVAL_DYN_ROW 18
+#define MAL_EVAL_DYN_MEAN 17
+#define MAL_EVAL_MASK_F32 0
+#define MAL_EVAL_MASK_U8 1
+typedef struct mal_eval_dyn_args {
+  int n_images, first, B, H, W;
+  int mh, mw, mask_dtype;       /* MAL_EVAL_MASK_* */
+  int gt_f64, reserved;
+  double min_depth, max_depth;  /* as the Python floats upstream passes to disp_to_depth: 1/min is formed in f64 */
+  const mal_eval_seg* seg;      /* device, [n_images] */
+  const int32_t* idx;           /* device, sparse flat indices (NULL if every segment is dense) */
+  const void* gt;               /* device, packed ground truth */
+  const float* disp;
+  const void* mask;
+  float* pred;
+  unsigned char* region;
+  float* scaled;                /* nullable */
+  double* img_out;              /* device, [n_images][MAL_EVAL_DYN_ROW] */
+  void* stream;
+} mal_eval_dyn_args;
+
+int mal_eval_dyn_accumulate(const mal_eval_dyn_args* args);
+/* out[0..6] the means of img_out[.][0..6] over the n_images images; out[7..13] the sums of img_out[.][7..13] over the images
+ * with n_doj > 0 divided by their number (NaN when there is none, upstream's 0/0); out[14] that number (doj/count);
+ * out[15] dojpxs, out[16] allpxs (the totals of n_doj and n_all).  In image order. */
+int mal_eval_dyn_mean(const double* img_out, int n_images, double* out, void* stream);
 
 /* ---- measurement hooks (bench.py): HIP events recorded immediately before / after the main
  * kernel of the NEXT mal_pass_fused call, on its stream (one-shot; cleared by that call). */

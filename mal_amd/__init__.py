@@ -8,7 +8,8 @@ operators raise.
 """
 __version__ = "0.1.0"
 
-__all__ = ["HungarianMatcher", "InstanceSegmenter", "Instances", "instance_inference", "MSDeformAttn", "ms_deform_attn"]
+__all__ = ["HungarianMatcher", "InstanceSegmenter", "Instances", "instance_inference", "MSDeformAttn", "ms_deform_attn",
+           "DynamicDepthEvaluator", "DynamicDepthValPath"]
 
 
 def __getattr__(name):
@@ -25,4 +26,8 @@ def __getattr__(name):
     if name in ("MSDeformAttn", "ms_deform_attn"):
         from . import msda
         return getattr(msda, name)
+    # DynamicDepth's validation metrics (mal_amd/dyn_eval.py), the same way
+    if name in ("DynamicDepthEvaluator", "DynamicDepthValPath"):
+        from . import dyn_eval
+        return getattr(dyn_eval, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

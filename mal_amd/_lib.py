@@ -137,6 +137,8 @@ SIGNATURES = {
     "mal_eval_mean": (i32, [vp, i32, vp, vp]),
     "mal_eval_errors_workspace_bytes": (sz, [sz]),
     "mal_eval_errors": (i32, [vp, i32, vp, i32, sz, vp, vp, sz, vp]),
+    "mal_eval_dyn_accumulate": (i32, [vp]),
+    "mal_eval_dyn_mean": (i32, [vp, i32, vp, vp]),
     "mal_match_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "mal_match": (i32, [vp]),
     "mal_instances_workspace_bytes": (sz, [i32] * 8),
@@ -229,6 +231,13 @@ class EvalArgs(C.Structure):
                 [(n, vp) for n in ("seg", "idx", "gt", "disp", "pred", "img_out", "stream")])
 
 
+class EvalDynArgs(C.Structure):
+    """mal_eval_dyn_args (include/mal_hip.h)."""
+    _fields_ = ([(n, i32) for n in ("n_images", "first", "B", "H", "W", "mh", "mw", "mask_dtype", "gt_f64", "reserved")] +
+                [(n, C.c_double) for n in ("min_depth", "max_depth")] +
+                [(n, vp) for n in ("seg", "idx", "gt", "disp", "mask", "pred", "region", "scaled", "img_out", "stream")])
+
+
 class MatchArgs(C.Structure):
     """mal_match_args (include/mal_hip.h)."""
     _fields_ = ([(n, vp) for n in ("masks_n", "masks_m", "masks_0")] +
@@ -261,6 +270,7 @@ class FwarpArgs(C.Structure):
                  ("ws", vp), ("ws_bytes", sz), ("stream", vp)])
 
 
+EVAL_DYN_ROW, EVAL_DYN_MEAN, EVAL_MASK_F32, EVAL_MASK_U8 = 18, 17, 0, 1
 FWARP_MAX_POSES, FWARP_MAX_UPSCALE, FWARP_MAX_C, FWARP_NO_REPROJ = 4, 4, 4, 1
 DR_MAX_ITERS = 4
 MATCH_MAX,MATCH_U8, MATCH_F32 = 128, 0, 1
@@ -301,7 +311,7 @@ def load():
     # the argument blocks are laid out twice (include/mal_hip.h, the ctypes Structures above): a stale library or a field added on
     # one side only must not get as far as a kernel launch
     for which, cls in enumerate((StepArgs, MsArgs, DrArgs, DynItem, StepScalesArgs, EvalSeg, EvalArgs, MatchArgs, InstancesArgs,
-                                 MsdaArgs, FwarpArgs)):
+                                 MsdaArgs, FwarpArgs, EvalDynArgs)):
         if lib.mal_struct_bytes(which) != C.sizeof(cls):
             raise MalError("%s: sizeof(%s) is %d in the library, %d in mal_amd/_lib.py -- rebuild (python -m mal_amd.build)"
                            % (LIB_PATH, cls.__name__, lib.mal_struct_bytes(which), C.sizeof(cls)))

@@ -32,6 +32,7 @@ extern "C" size_t mal_struct_bytes(int which) {
     case 8: return sizeof(mal_instances_args);
     case 9: return sizeof(mal_msda_args);
     case 10: return sizeof(mal_fwarp_args);
+    case 11: return sizeof(mal_eval_dyn_args);
     default: return 0;
   }
 }
