@@ -10,21 +10,16 @@
 //                              of compute_depth_errors over all valid points and over those inside the object region
 //   mal_eval_dyn_mean        Trainer.val's aggregation over the rows, in image order
 //
-// The select, the scan and the fixed-order sums are csrc/mal_eval.hip's, restated here so that file compiles as it did
-// (DESIGN.md 19); the decisions are taken in the dtype torch takes them in.  Nothing is allocated, read back or
-// synchronised; a batch writes only its own images' rows, so grouping and order of the batches do not matter.
-#include "mal_common.h"
-#include "mal_device.h"
+// The select, the scan, the packed-slot decode, the per-point terms and the promoted means are csrc/mal_eval_core.h's, shared
+// with csrc/mal_eval.hip; this file holds what is DynamicDepth's: the decisions are taken in the dtype torch
+// takes them in.  Nothing is allocated, read back or synchronised; a batch writes only its own images' rows, so grouping and
+// order of the batches do not matter.
+#include "mal_eval_core.h"
 
 using namespace mal;
 
 namespace {
 
-constexpr int kImgThreads = 1024;   // per-image workgroup: 16 waves
-constexpr int kImgWaves = kImgThreads / 64;
-constexpr int kPredThreads = 256;
-constexpr int kPredBlocksPerImage = 32;
-constexpr uint32_t kInvalid = 0xffffffffu;  // pred slot of a dense pixel outside the mask
 constexpr int kRow = MAL_EVAL_DYN_ROW;
 constexpr int kSums = 8, kCounts = 8;       // 4 + 4 sums; 3 + 3 threshold counts, n_all, n_doj
 constexpr float kClampMin = 1e-3f, kClampMax = 80.f;  // trainer.py:1189, :1220: literals, not options
@@ -35,9 +30,6 @@ MAL_DEV float clamp_t(float v) {
   if (v > kClampMax) v = kClampMax;
   return v;
 }
-
-// torch.log of a float32 tensor, as the correctly rounded value
-MAL_DEV float logf_cr(float x) { return (float)log((double)x); }
 
 // ATen's area_pixel_compute_source_index (align_corners=False, not cubic) and the taps of upsample_bilinear2d's device
 // kernel: src = max(0, scale * (dst + 0.5) - 0.5), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1
@@ -68,16 +60,9 @@ __global__ __launch_bounds__(kPredThreads) void eval_dyn_predict_kernel(mal_eval
   const float sy = (float)a.H / (float)sg.gt_h, sx = (float)a.W / (float)sg.gt_w;
   const float my = (float)a.mh / (float)sg.gt_h, mx = (float)a.mw / (float)sg.gt_w;
   for (int i = blockIdx.x * kPredThreads + threadIdx.x; i < sg.slots; i += gridDim.x * kPredThreads) {
+    if (sg.dense && !(g[i] > (T)0)) { out[i] = kInvalid; reg[i] = 0; continue; }
     int x, y;
-    if (sg.dense) {
-      if (!(g[i] > (T)0)) { out[i] = kInvalid; reg[i] = 0; continue; }
-      y = sg.y0 + i / sg.rw;
-      x = sg.x0 + (i - (i / sg.rw) * sg.rw);
-    } else {
-      const int f = a.idx[sg.off + i];
-      y = f / sg.gt_w;
-      x = f - y * sg.gt_w;
-    }
+    slot_xy(sg, a.idx, i, x, y);
     int y0, y1, x0, x1;
     float l0y, l1y, l0x, l1x;
     taps_of(sy, y, a.H, y0, y1, l0y, l1y);
@@ -91,73 +76,10 @@ __global__ __launch_bounds__(kPredThreads) void eval_dyn_predict_kernel(mal_eval
   }
 }
 
-// exclusive prefix sum over the workgroup (wave scan with shuffles, then the waves in order)
-__device__ int block_excl_scan(int v, int* s_wave) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[w] = x;
-  __syncthreads();
-  int b = 0;
-  for (int i = 0; i < w; ++i) b += s_wave[i];
-  __syncthreads();
-  return b + x - v;
-}
-
-MAL_DEV double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// one point's four terms and three comparisons of compute_depth_errors under torch's promotion: f64 arithmetic when the
-// ground truth is f64 (the float32 prediction is widened), torch.log in each operand's own dtype
-template <typename G>
-MAL_DEV void point_terms(G g, float p, double* t, int* c) {
-  if constexpr (sizeof(G) == 8) {
-    const double gd = (double)g, pd = (double)p;
-    const double d = gd - pd;
-    t[0] = fabs(d) / gd;
-    t[1] = (d * d) / gd;
-    t[2] = d * d;
-    const double l = log(gd) - (double)logf_cr(p);
-    t[3] = l * l;
-    const double th = fmax(gd / pd, pd / gd);
-    c[0] = th < 1.25 ? 1 : 0;
-    c[1] = th < 1.5625 ? 1 : 0;
-    c[2] = th < 1.953125 ? 1 : 0;
-  } else {
-    const float gf = (float)g;
-    const float d = gf - p;
-    t[0] = (double)(fabsf(d) / gf);
-    t[1] = (double)((d * d) / gf);
-    t[2] = (double)(d * d);
-    const float l = logf_cr(gf) - logf_cr(p);
-    t[3] = (double)(l * l);
-    const float th = fmaxf(gf / p, p / gf);
-    c[0] = th < 1.25f ? 1 : 0;
-    c[1] = th < 1.5625f ? 1 : 0;
-    c[2] = th < 1.953125f ? 1 : 0;
-  }
-}
-
 // one region's metrics from its sums: the four means in the promoted dtype; a1..a3 are .float().mean(): count / n in
 // float32 (both exact below 2^24, which the packing guarantees)
 MAL_DEV void finish_errors(const double* s4, const int* c3, int ni, bool f32, double* out) {
-  const double n = (double)ni;
-  if (f32) {
-    out[0] = (double)(float)(s4[0] / n);
-    out[1] = (double)(float)(s4[1] / n);
-    out[2] = (double)sqrtf((float)(s4[2] / n));
-    out[3] = (double)sqrtf((float)(s4[3] / n));
-  } else {
-    out[0] = s4[0] / n;
-    out[1] = s4[1] / n;
-    out[2] = sqrt(s4[2] / n);
-    out[3] = sqrt(s4[3] / n);
-  }
+  finish_means4(s4, (double)ni, f32, out);
   for (int k = 0; k < 3; ++k) out[4 + k] = (double)((float)c3[k] / (float)ni);
 }
 
@@ -180,39 +102,8 @@ __global__ __launch_bounds__(kImgThreads) void eval_dyn_image_kernel(mal_eval_dy
   constexpr bool gt64 = sizeof(T) == 8;
   if (tid == 0) { s_bin = 0; s_below = 0; }
 
-  // torch.median: element (n - 1) / 2 of the sorted values.  Radix select on the bits of positive floats (monotone; the
-  // clamp leaves them in [1e-3, 80]): 12 + 12 + 8 bits
-  uint32_t prefix = 0, pmask = 0;
-  int k = (sg.n - 1) / 2;
-  for (int pass = 0; pass < 3; ++pass) {
-    const int shift = pass == 0 ? 20 : (pass == 1 ? 8 : 0);
-    const int nb = pass == 2 ? 256 : 4096;
-    for (int i = tid; i < nb; i += kImgThreads) hist[i] = 0u;
-    __syncthreads();
-    for (int i = tid; i < sg.slots; i += kImgThreads) {
-      const uint32_t u = pb[i];
-      if (u != kInvalid && (u & pmask) == prefix) atomicAdd(&hist[(u >> shift) & (uint32_t)(nb - 1)], 1u);
-    }
-    __syncthreads();
-    const int per = (nb + kImgThreads - 1) / kImgThreads;
-    const int b0 = tid * per, b1 = min(b0 + per, nb);
-    int local = 0;
-    for (int b = b0; b < b1; ++b) local += (int)hist[b];
-    const int excl = block_excl_scan(local, s_wave);
-    if (k >= excl && k < excl + local) {
-      int c = excl;
-      for (int b = b0; b < b1; ++b) {
-        if (k < c + (int)hist[b]) { s_bin = b; s_below = c; break; }
-        c += (int)hist[b];
-      }
-    }
-    __syncthreads();
-    prefix |= (uint32_t)s_bin << shift;
-    pmask |= (uint32_t)(nb - 1) << shift;
-    k -= s_below;
-    __syncthreads();
-  }
-  const float med = __uint_as_float(prefix);
+  // torch.median: element (n - 1) / 2 of the sorted values (the clamp leaves them in [1e-3, 80]: positive floats)
+  const float med = __uint_as_float(radix_select(pb, sg.slots, (sg.n - 1) / 2, hist, s_wave, &s_bin, &s_below).bits);
   // depth_pred *= median(gt[mask]) / median(depth_pred[mask]): the quotient of two 0-dim tensors is taken in their promoted
   // dtype (f64 with f64 ground truth); the in-place multiply of the float32 map casts that 0-dim operand to float32 first
   // (TensorIterator's common dtype is the dimensioned operand's), so the ratio is rounded to float32 BEFORE the multiply
@@ -233,7 +124,7 @@ __global__ __launch_bounds__(kImgThreads) void eval_dyn_image_kernel(mal_eval_dy
     if (scaled) scaled[i] = p;
     double t[4];
     int f[3];
-    point_terms<T>(gt[i], p, t, f);
+    point_terms<T, float>(gt[i], p, t, f);
     const bool in = reg[i] != 0;  // the object region takes the same terms: sums per thread in f64 (f64's own for f64 ground truth)
     for (int q = 0; q < 4; ++q) {
       s[q] += t[q];
@@ -249,7 +140,7 @@ __global__ __launch_bounds__(kImgThreads) void eval_dyn_image_kernel(mal_eval_dy
   // fixed shuffle tree, then the waves in order
   const int lane = tid & 63, w = tid >> 6;
   for (int q = 0; q < kSums; ++q) {
-    const double t = wave_sum(s[q]);
+    const double t = wave_sum_d(s[q]);
     if (lane == 0) s_red[q][w] = t;
   }
   for (int q = 0; q < kCounts; ++q) {

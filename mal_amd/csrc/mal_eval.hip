@@ -10,23 +10,14 @@
 // Every sum is per thread in a fixed stride order, then a fixed shuffle tree, then the waves in order: the same inputs give
 // the same bits, and a batch writes only its own images' slots, so the order in which batches arrive does not matter.
 // Decisions (median, ratio, clamp, thresh < 1.25^k) are taken in the dtype numpy takes them in (DESIGN.md "Validation").
-#include "mal_common.h"
-#include "mal_device.h"
+#include "mal_eval_core.h"
 
 using namespace mal;
 
 namespace {
 
-constexpr int kImgThreads = 1024;   // per-image workgroup: 16 waves
-constexpr int kImgWaves = kImgThreads / 64;
-constexpr int kPredThreads = 256;
-constexpr int kPredBlocksPerImage = 32;
 constexpr int kErrThreads = 256;
 constexpr int kErrBlocks = 1024;
-constexpr uint32_t kInvalid = 0xffffffffu;  // pred slot of a dense pixel outside the mask
-
-// np.log of a float32 array, as the correctly rounded value (numpy's SIMD logf is within a few ulp of it)
-MAL_DEV float logf_cr(float x) { return (float)log((double)x); }
 
 // the scaled disparity of disp_to_depth at a source pixel (mal_disp_to_depth's arithmetic)
 MAL_DEV float scaled_at(const float* __restrict__ S, int i, float min_disp, float range) {
@@ -72,16 +63,9 @@ __global__ __launch_bounds__(kPredThreads) void eval_predict_kernel(mal_eval_arg
   const T* g = (const T*)a.gt + sg.off;
   const double scale_x = 1.0 / ((double)sg.gt_w / (double)a.W), scale_y = 1.0 / ((double)sg.gt_h / (double)a.H);
   for (int i = blockIdx.x * kPredThreads + threadIdx.x; i < sg.slots; i += gridDim.x * kPredThreads) {
+    if (sg.dense && !(g[i] > (T)0)) { out[i] = kInvalid; continue; }
     int x, y;
-    if (sg.dense) {
-      if (!(g[i] > (T)0)) { out[i] = kInvalid; continue; }
-      y = sg.y0 + i / sg.rw;
-      x = sg.x0 + (i - (i / sg.rw) * sg.rw);
-    } else {
-      const int f = a.idx[sg.off + i];
-      y = f / sg.gt_w;
-      x = f - y * sg.gt_w;
-    }
+    slot_xy(sg, a.idx, i, x, y);
     float v = resize_at(S, a.H, a.W, scale_x, scale_y, x, y, min_disp, range);
     if (a.resize_ulp) v = __uint_as_float(__float_as_uint(v) + (uint32_t)a.resize_ulp);  // v > 0: bits are monotone
     const float p = div_(1.0f, v) * a.scale_factor;  // pred_depth = 1 / pred_disp; *= pred_depth_scale_factor
@@ -89,79 +73,30 @@ __global__ __launch_bounds__(kPredThreads) void eval_predict_kernel(mal_eval_arg
   }
 }
 
-// exclusive prefix sum over the workgroup (wave scan with shuffles, then the waves in order)
-__device__ int block_excl_scan(int v, int* s_wave) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[w] = x;
-  __syncthreads();
-  int b = 0;
-  for (int i = 0; i < w; ++i) b += s_wave[i];
-  __syncthreads();
-  return b + x - v;
-}
-
-MAL_DEV double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // the four sums and three counts of compute_errors, accumulated in f64 per thread
 struct ErrSums {
   double abs_rel = 0.0, sq_rel = 0.0, sq = 0.0, sq_log = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
 };
 
-// gt and pred in their own dtypes; logs in those dtypes, everything else in f64 if either is f64
+// gt and pred in their own dtypes (point_terms); the counts are kept as doubles
 template <typename G, typename P>
 MAL_DEV void add_point(ErrSums& s, G g, P p) {
-  constexpr bool f64 = sizeof(G) == 8 || sizeof(P) == 8;
-  if constexpr (f64) {
-    const double gd = (double)g, pd = (double)p;
-    const double d = gd - pd;
-    s.abs_rel += fabs(d) / gd;
-    s.sq_rel += (d * d) / gd;
-    s.sq += d * d;
-    const double lgg = sizeof(G) == 8 ? log(gd) : (double)logf_cr((float)g);
-    const double lgp = sizeof(P) == 8 ? log(pd) : (double)logf_cr((float)p);
-    const double l = lgg - lgp;
-    s.sq_log += l * l;
-    const double th = fmax(gd / pd, pd / gd);
-    s.c1 += th < 1.25 ? 1.0 : 0.0;
-    s.c2 += th < 1.5625 ? 1.0 : 0.0;
-    s.c3 += th < 1.953125 ? 1.0 : 0.0;
-  } else {
-    const float gf = (float)g, pf = (float)p;
-    const float d = gf - pf;
-    s.abs_rel += (double)(fabsf(d) / gf);
-    s.sq_rel += (double)((d * d) / gf);
-    s.sq += (double)(d * d);
-    const float l = logf_cr(gf) - logf_cr(pf);
-    s.sq_log += (double)(l * l);
-    const float th = fmaxf(gf / pf, pf / gf);
-    s.c1 += th < 1.25f ? 1.0 : 0.0;
-    s.c2 += th < 1.5625f ? 1.0 : 0.0;
-    s.c3 += th < 1.953125f ? 1.0 : 0.0;
-  }
+  double t[4];
+  int c[3];
+  point_terms<G, P>(g, p, t, c);
+  s.abs_rel += t[0];
+  s.sq_rel += t[1];
+  s.sq += t[2];
+  s.sq_log += t[3];
+  s.c1 += (double)c[0];
+  s.c2 += (double)c[1];
+  s.c3 += (double)c[2];
 }
 
 // per-image metrics from the sums: f64 as numpy's means; with float32 arithmetic the four means are float32 (a1..a3 are
 // means of booleans: f64 either way)
 MAL_DEV void finish_errors(const double* s7, double n, bool f32, double* out) {
-  if (f32) {
-    out[0] = (double)(float)(s7[0] / n);
-    out[1] = (double)(float)(s7[1] / n);
-    out[2] = (double)sqrtf((float)(s7[2] / n));
-    out[3] = (double)sqrtf((float)(s7[3] / n));
-  } else {
-    out[0] = s7[0] / n;
-    out[1] = s7[1] / n;
-    out[2] = sqrt(s7[2] / n);
-    out[3] = sqrt(s7[3] / n);
-  }
+  finish_means4(s7, n, f32, out);
   out[4] = s7[4] / n;
   out[5] = s7[5] / n;
   out[6] = s7[6] / n;
@@ -172,7 +107,7 @@ __device__ void block_sum7(const ErrSums& s, double (*s_red)[kImgWaves], int nwa
   const double v[7] = {s.abs_rel, s.sq_rel, s.sq, s.sq_log, s.c1, s.c2, s.c3};
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int k = 0; k < 7; ++k) {
-    const double t = wave_sum(v[k]);
+    const double t = wave_sum_d(v[k]);
     if (lane == 0) s_red[k][w] = t;
   }
   __syncthreads();
@@ -203,44 +138,13 @@ __global__ __launch_bounds__(kImgThreads) void eval_image_kernel(mal_eval_args a
   double ratio = 1.0;
   float ratio_f = 1.0f;
   if (a.median_scaling) {
-    // radix select of rank k1 = (n-1)/2 on the bits of positive floats (monotone): 12 + 12 + 8 bits
+    // np.median's lower middle value: rank k1 = (n-1)/2
     const int n = sg.n, k1 = (n - 1) / 2;
-    uint32_t prefix = 0, pmask = 0;
-    int k = k1, cnt_eq = 0;
-    for (int pass = 0; pass < 3; ++pass) {
-      const int shift = pass == 0 ? 20 : (pass == 1 ? 8 : 0);
-      const int nb = pass == 2 ? 256 : 4096;
-      for (int i = tid; i < nb; i += kImgThreads) hist[i] = 0u;
-      __syncthreads();
-      for (int i = tid; i < sg.slots; i += kImgThreads) {
-        const uint32_t u = pb[i];
-        if (u != kInvalid && (u & pmask) == prefix) atomicAdd(&hist[(u >> shift) & (uint32_t)(nb - 1)], 1u);
-      }
-      __syncthreads();
-      const int per = (nb + kImgThreads - 1) / kImgThreads;
-      const int b0 = tid * per, b1 = min(b0 + per, nb);
-      int local = 0;
-      for (int b = b0; b < b1; ++b) local += (int)hist[b];
-      const int excl = block_excl_scan(local, s_wave);
-      if (k >= excl && k < excl + local) {
-        int c = excl;
-        for (int b = b0; b < b1; ++b) {
-          if (k < c + (int)hist[b]) { s_bin = b; s_below = c; break; }
-          c += (int)hist[b];
-        }
-      }
-      __syncthreads();
-      const int b = s_bin;
-      prefix |= (uint32_t)b << shift;
-      pmask |= (uint32_t)(nb - 1) << shift;
-      k -= s_below;
-      if (pass == 2) cnt_eq = (int)hist[b];
-      __syncthreads();
-    }
-    const uint32_t v1 = prefix;
+    const Selected sel = radix_select(pb, sg.slots, k1, hist, s_wave, &s_bin, &s_below);
+    const uint32_t v1 = sel.bits;
     uint32_t v2 = v1;
     // even count: the upper middle is v1 again unless every copy of v1 lies at or below rank k1
-    if ((n & 1) == 0 && (k1 - k) + cnt_eq < k1 + 2) {
+    if ((n & 1) == 0 && (k1 - sel.k_left) + sel.cnt_eq < k1 + 2) {
       if (tid == 0) s_min = kInvalid;
       __syncthreads();
       uint32_t m = kInvalid;

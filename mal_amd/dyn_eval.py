@@ -7,7 +7,7 @@ region** (``doj/abs_rel`` .. ``doj/a3``), for the student and for the teacher.  
 ``val`` and differs from this rule in every step (the disparity is resized there, the depth here; ``np.median`` there,
 ``torch.median``'s lower middle value here; one region there, two here), so this evaluator stands beside it.
 
-``DynamicDepthEvaluator`` packs a split's ground truth once with ``DepthEvaluator``'s own packing, then takes disparities and
+``DynamicDepthEvaluator`` packs a split's ground truth once with ``evaluate.pack_ground_truth``, then takes disparities and
 object masks batch by batch -- any batch size; upstream can only do one image at a time -- on the caller's stream with no host
 synchronisation.  The results do not depend on the order or grouping of the batches.
 """
@@ -19,14 +19,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluate import METRICS, DepthEvaluator
+from .evaluate import METRICS, _planes, _SplitEvaluator, pack_ground_truth
 
 __all__ = ["DynamicDepthEvaluator", "DynamicDepthValPath", "METRICS"]
 
 _MAX_POINTS = 1 << 24   # a1..a3 are float32 means of 0/1: exact below 2^24 points per image
 
 
-class DynamicDepthEvaluator:
+class DynamicDepthEvaluator(_SplitEvaluator):
     """The per-image rule of ``compute_depth_losses`` and ``val``'s aggregation for one split.
 
     ``gt_depths``: the split's ground truth, a list of 2-D numpy arrays, all float64 or all float32.  ``eval_split``: "eigen"
@@ -35,6 +35,7 @@ class DynamicDepthEvaluator:
     ``min_depth`` / ``max_depth``: the 1e-3 and 80 upstream has as literals for the ground-truth mask and both clamps.
     An image without a valid pixel raises ValueError (upstream's medians of an empty slice fail); so does one with 2^24 or more.
     """
+    ROW = _lib.EVAL_DYN_ROW
 
     def __init__(self, gt_depths, eval_split, device="cuda", min_depth=1e-3, max_depth=80):
         if eval_split not in ("eigen", "eigen_benchmark", "cityscapes"):
@@ -44,36 +45,15 @@ class DynamicDepthEvaluator:
             raise ValueError("DynamicDepthEvaluator: upstream's 1e-3 and 80 are literals (trainer.py:1164-1165, :1189, :1220); the "
                              "kernels clamp to them")
         self.split, self.device = eval_split, torch.device(device)
-        # DepthEvaluator's packing, on the host: the same segments, indices and values
-        pk = DepthEvaluator(gt_depths, "eigen" if eval_split == "eigen_benchmark" else eval_split, "cpu", min_depth, max_depth)
-        self.n_images, self.gt_f64, self.offsets, self.counts = pk.n_images, pk.gt_f64, pk.offsets, pk.counts
-        segs = (_lib.EvalSeg * pk.n_images).from_buffer_copy(pk.seg.numpy().tobytes())
-        vals = pk.gt.numpy()
-        for i in range(pk.n_images):
-            s = segs[i]
-            if s.n >= _MAX_POINTS:
+        pk = pack_ground_truth(gt_depths, "eigen" if eval_split == "eigen_benchmark" else eval_split, min_depth, max_depth,
+                               median="lower")   # torch.median: the lower middle value
+        for i, n in enumerate(pk.counts):
+            if n >= _MAX_POINTS:
                 raise ValueError("DynamicDepthEvaluator: image %d has %d valid points; the float32 means a1..a3 are exact below "
-                                 "%d only" % (i, s.n, _MAX_POINTS))
-            v = vals[s.off:s.off + s.slots]
-            if s.dense:
-                v = v[v > 0]
-            s.med_gt = float(np.partition(v, (s.n - 1) // 2)[(s.n - 1) // 2])   # torch.median: the lower middle value
+                                 "%d only" % (i, n, _MAX_POINTS))
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise _lib.MalError("DynamicDepthEvaluator: needs a HIP device (there is no CPU path), got %r" % (device,))
-        self.gt, self.idx = pk.gt.to(self.device), pk.idx.to(self.device)
-        self.seg = torch.frombuffer(bytearray(bytes(segs)), dtype=torch.uint8).to(self.device)
-        self.reset()
-
-    def reset(self):
-        self._out, self._fed = {}, {}
-
-    def _slot(self, which):
-        if which not in ("student", "mono"):
-            raise ValueError("which: 'student' or 'mono', got %r" % (which,))
-        if which not in self._out:
-            self._out[which] = torch.zeros(self.n_images, _lib.EVAL_DYN_ROW, dtype=torch.float64, device=self.device)
-            self._fed[which] = np.zeros(self.n_images, bool)
-        return self._out[which]
+        self._upload(pk)
 
     def accumulate(self, disp, doj_mask, first_index, which="student", disp_min=0.1, disp_max=100.0, export=False):
         """One batch: ``disp`` (B,1,h,w) or (B,h,w) float32 sigmoid outputs (``outputs[("disp", 0)]``, or ``("mono_disp", 0)``
@@ -84,30 +64,16 @@ class DynamicDepthEvaluator:
         scaling and the second clamp} (slots of the batch's segments in order; dense slots outside the mask hold NaN bits /
         0 / 0)."""
         out = self._slot(which)
-        if not isinstance(disp, torch.Tensor) or disp.device.type != "cuda" or disp.dtype != torch.float32:
-            raise _lib.MalError("accumulate: disp must be a float32 device tensor (there is no CPU path)")
+        disp = self._disp_planes(disp)
         if not isinstance(doj_mask, torch.Tensor) or doj_mask.device != disp.device:
             raise _lib.MalError("accumulate: doj_mask must be a tensor on disp's device")
         if doj_mask.dtype not in (torch.float32, torch.uint8):
             raise TypeError("accumulate: doj_mask must be float32 or uint8, got %s" % doj_mask.dtype)
-
-        def planes(t, what):
-            if t.dim() == 4:
-                if t.shape[1] != 1:
-                    raise ValueError("accumulate: %s must be (B,1,h,w), got %s" % (what, tuple(t.shape)))
-                t = t[:, 0]
-            if t.dim() != 3:
-                raise ValueError("accumulate: %s must be (B,1,h,w) or (B,h,w), got %s" % (what, tuple(t.shape)))
-            return t.contiguous()
-
-        disp, doj_mask = planes(disp, "disp"), planes(doj_mask, "doj_mask")
+        doj_mask = _planes(doj_mask, "doj_mask")
         B, H, W = disp.shape
         if doj_mask.shape[0] != B:
             raise ValueError("accumulate: %d disparities, %d masks" % (B, doj_mask.shape[0]))
-        first = int(first_index)
-        if first < 0 or first + B > self.n_images:
-            raise IndexError("accumulate: images %d..%d outside the split's %d" % (first, first + B - 1, self.n_images))
-        slots = int(self.offsets[first + B] - self.offsets[first])
+        first, slots = self._batch(first_index, B)
         pred = torch.empty(slots, dtype=torch.float32, device=self.device)
         region = torch.empty(slots, dtype=torch.uint8, device=self.device)
         scaled = torch.empty(slots, dtype=torch.float32, device=self.device) if export else None
@@ -136,9 +102,7 @@ class DynamicDepthEvaluator:
         object means, as upstream's 0/0 does.  The sums run in image order in float64 (upstream's accumulator takes a1..a3 in
         float32 or float64 depending on numpy's promotion rules).  Synchronises."""
         out = self.rows(which)
-        missing = np.nonzero(~self._fed[which])[0]
-        if missing.size:
-            raise RuntimeError("result(%r): %d image(s) never accumulated, first %d" % (which, missing.size, missing[0]))
+        self._all_fed(which)
         mean = torch.empty(_lib.EVAL_DYN_MEAN, dtype=torch.float64, device=self.device)
         _lib.check(_lib.load().mal_eval_dyn_mean(out.data_ptr(), self.n_images, mean.data_ptr(),
                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mal_eval_dyn_mean")

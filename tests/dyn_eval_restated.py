@@ -226,6 +226,7 @@ SWEEP_CASES = {
     "d5x1":      ("eigen", (5, 1), (9, 13), "f8", (5, 1), "u1", (3, 4, 1), (0.1, 100.0), 0),
     "d2x2":      ("eigen", (2, 2), (9, 13), "f4", (9, 13), "f4", (2,), (0.1, 100.0), 0),
     "same6x10":  ("eigen", (6, 10), (6, 10), "f8", (6, 10), "f4", (4, 3, 2), (0.1, 100.0), 0),
+    "ulps6x10":  ("eigen", (6, 10), (6, 10), "f4", (6, 10), "u1", (9, 8, 6), (0.1, 100.0), 0),   # odd, even, all equal (below)
     "up7x11":    ("eigen", (6, 10), (7, 11), "f4", (3, 4), "u1", (24,), (0.1, 100.0), 0),
     "up12x20":   ("eigen", (3, 5), (12, 20), "f8", (3, 5), "f4", (40, 41, 17), (0.1, 100.0), 0),
     "clamps":    ("eigen", (3, 5), (12, 20), "f4", (6, 10), "f4", (60, 61, 33), (5e-4, 100.0), 0),
@@ -240,6 +241,9 @@ GOLDEN_CASES = {
     "eigen_3x5":   ("eigen_benchmark", (3, 5), (12, 20), "f8", (6, 10), "f4", (36, 37, 20), (0.1, 100.0), 0),
     "cityscapes":  ("cityscapes", (12, 32), (1024, 2048), "f4", (12, 32), "f4", (300, 301), (0.1, 100.0), 1),
 }
+
+
+ULPS_BASE = np.float32(0.00901)   # disp_to_depth(., 0.1, 100) = 9.99901, bits 0x411ffbf2
 
 
 def valid_region(split, H, W):
@@ -283,6 +287,12 @@ def make_case(name, table=None, seed=None):
             d = d ** 3 * 0.01
             d[:, 0, 1, 0:2] = 0.0      # depth 100 -> clamped at 80
             d[:, 0, 2, 3:5] = 1.0      # depth 5e-4 -> clamped at 1e-3
+        if name == "ulps6x10":
+            # same size: the taps are (1, 0), a prediction is the depth of its own pixel.  Disparities two ulp apart from
+            # ULPS_BASE give distinct depths within 116 float32 values below 9.99901, which share their top 24 bits: only
+            # the select's last 8-bit pass tells them apart.  The third image's are all equal.
+            steps = np.stack([2 * rng.permutation(h * w) if i < 2 else np.zeros(h * w, np.int64) for i in range(B)])
+            return torch.from_numpy((ULPS_BASE.view(np.int32) + steps.astype(np.int32)).view(np.float32).reshape(B, 1, h, w))
         return torch.from_numpy(d.astype(np.float32))
 
     disp, mono = disparity(), disparity()

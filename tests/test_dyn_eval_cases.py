@@ -195,6 +195,21 @@ def test_named_cases_have_their_property(sweep):
     # tied predictions around the median, on an even count
     r = sweep["eigen1024"][1][("student", "aten")][1]
     assert r["n_all"] % 2 == 0 and len(torch.unique(r["pred_first"])) < r["n_all"]
+    # ulps6x10: an odd count, an even count and all predictions equal; each image's predictions are its own pixels' depths,
+    # share their top 24 bits (the first two passes of the 12 + 12 + 8 bit select see one bin) and the median is the lower
+    # middle value, which on the even count is not the upper one
+    c, ev = sweep["ulps6x10"]
+    for (w, rs), res in ev.items():
+        assert [r["n_all"] % 2 for r in res[:2]] == [1, 0], (w, rs)
+        depth = R.disp_to_depth(c["disp" if w == "student" else "mono_disp"], c["min_depth"], c["max_depth"])
+        for i, r in enumerate(res):
+            p, n = r["pred_first"], r["n_all"]
+            assert torch.equal(p, depth[i, 0][r["mask"]]), (w, rs, i)   # taps (1, 0), no clamp
+            assert len(np.unique(bits(p) >> 8)) == 1 and len(np.unique(bits(p))) == (1 if i == 2 else n), (w, rs, i)
+            order = torch.sort(p)[0]
+            assert float(p[r["median_index"]]) == float(order[(n - 1) // 2]) == float(r["median"]), (w, rs, i)
+        assert res[1]["median"] < torch.sort(res[1]["pred_first"])[0][res[1]["n_all"] // 2], (w, rs)
+        assert res[2]["median_index"] == (res[2]["n_all"] - 1) // 2, (w, rs)   # all equal: the stable order's middle
 
 
 def test_each_variant_moves_a_case(sweep):
