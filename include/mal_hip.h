@@ -706,6 +706,36 @@ int mal_stem_pool_fwd(const float* y, float* p, uint8_t* code, int B, int C, int
 int mal_stem_pool_bwd(const float* g_p, const float* g_y, const uint8_t* code, float* dy, int B, int C, int H, int W,
                       void* stream);
 
+/* ---- torch.optim.Adam's update (plain Adam: no weight decay, no amsgrad, no maximize) over a flat gradient buffer as ONE
+ * launch (mal_amd/optim.py: FlatAdam).  The parameters stay where they are: `table` is a DEVICE array of n_chunks entries, one
+ * per parameter tensor (fp32, contiguous): where it lives, the offset of its gradient in `grad` -- and of its moments in
+ * exp_avg / exp_avg_sq, flat buffers of flat_elements floats each with the same offsets -- and its element count.  A call
+ * updates the entries [first, first + count) (count 0: MAL_OK, no launch); range_elements, the sum of their counts, sizes the
+ * grid and nothing else.  Per element, fp32, every operator one correctly rounded operation, no fused multiply-add, ATen's order:
+ *   m' = m + (g - m) * c1;  v' = v * beta2 + (c2 * g) * g;  den = sqrt(v') / bs + eps;  p' = p + a * (m' / den)
+ * with c1 = 1 - beta1, c2 = 1 - beta2, bs = sqrt(1 - beta2^t), a = -lr / (1 - beta1^t) formed by the caller in double and
+ * rounded once.  t (the step number, >= 1) is checked, not used.  zero_grad != 0: each gradient element is overwritten with
+ * +0 after it was read.  16-byte accesses with the flat side on the 16-byte grid, the 0..3 elements in front of and behind
+ * them one by one; nothing outside a chunk is read or written, and an entry with a null pointer or with offset + count >
+ * flat_elements is skipped.  No atomics: bit-reproducible, and any split into consecutive ranges gives the same bits.
+ * The planning function is pure host code: the workgroups (at most 2048, tile T of the range belongs to workgroup T % blocks)
+ * and threads of the launch for a range of n_chunks entries with total_elements elements, the elements of a tile (2048: a
+ * chunk's tile 0 also owns its head and tail), the entries staged in LDS at a time and sizeof(mal_adam_chunk); every output
+ * pointer is nullable.
+ * MAL_EINVAL: a null pointer; a table off the 8-byte or a flat buffer off the 4-byte grid; n_chunks < 1; a range outside the
+ * table; flat_elements < 1 or a total of 2^31 elements or more (32-bit offsets); range_elements < 0 or > flat_elements;
+ * t < 1; bs not finite or not positive.  All checked before any HIP call. */
+typedef struct mal_adam_chunk {
+  float* param;      /* the parameter tensor's storage */
+  uint32_t offset;   /* of its gradient and moments in the flat buffers, in elements */
+  uint32_t count;    /* elements */
+} mal_adam_chunk;
+int mal_adam_plan(int n_chunks, long long total_elements, int* blocks, int* threads, int* tile_elements, int* table_window,
+                  int* chunk_bytes);
+int mal_adam_flat(const mal_adam_chunk* table, int n_chunks, int first, int count, long long range_elements, float* grad,
+                  float* exp_avg, float* exp_avg_sq, long long flat_elements, int t, float c1, float beta2, float c2, float bs,
+                  float eps, float a, int zero_grad, void* stream);
+
 /* ---- N2: the temporal-hint producer's per-sample arithmetic, manydepth/dyn_utils.py:6-119 --------
  * (fill_dynamic_obj + generate_dynamic_instance), given the matched instance masks of the two warped frames
  * (num,H,W as bytes, non-zero = set; Mask2Former stays outside, the matcher is mal_match below).  Per instance the displacement

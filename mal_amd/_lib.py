@@ -122,6 +122,9 @@ SIGNATURES = {
     "mal_stem_pool_plan": (i32, [i32, i32, i32, i32, i32] + [C.POINTER(i32)] * 6),
     "mal_stem_pool_fwd": (i32, [c_fp, c_fp, vp, i32, i32, i32, i32, vp]),
     "mal_stem_pool_bwd": (i32, [c_fp, c_fp, vp, c_fp, i32, i32, i32, i32, vp]),
+    "mal_adam_plan": (i32, [i32, C.c_longlong] + [C.POINTER(i32)] * 5),
+    "mal_adam_flat": (i32, [vp, i32, i32, i32, C.c_longlong, c_fp, c_fp, c_fp, C.c_longlong, i32, f32, f32, f32, f32, f32, f32,
+                            i32, vp]),
     "mal_set_option": (i32, [C.c_char_p, i32]),
     "mal_get_option": (i32, [C.c_char_p, C.POINTER(i32)]),
     "mal_build_has_experiments": (i32, []),
@@ -151,6 +154,11 @@ SIGNATURES = {
     "mal_forward_warp": (i32, [vp]),
     "mal_inverse_warp": (i32, [c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp, vp, vp, sz, vp]),
 }
+
+class AdamChunk(C.Structure):
+    """mal_adam_chunk (include/mal_hip.h); mal_adam_plan reports the library's sizeof."""
+    _fields_ = [("param", vp), ("offset", C.c_uint32), ("count", C.c_uint32)]
+
 
 class DynItem(C.Structure):
     """mal_dyn_item (include/mal_hip.h)."""

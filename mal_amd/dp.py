@@ -114,9 +114,11 @@ class FlatGradBucket:
         return None
 
     # ---- the exchange overlapped with the backward
-    def begin_step(self):
-        """zero the gradients and arm the pieces for the backward that follows"""
-        self.flat.zero_()
+    def begin_step(self, zero=True):
+        """zero the gradients and arm the pieces for the backward that follows; ``zero=False``: the caller vouches that the
+        buffer is zero already (``mal_amd.optim.FlatAdam.step(zero_grad=True)`` left it so)"""
+        if zero:
+            self.flat.zero_()
         if len(self.bounds) > 1 and self.world_size > 1:
             self._use_avg()  # the probe collective, if any, happens here on every rank -- not inside a hook
             self._pending = list(self._count)

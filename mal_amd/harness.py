@@ -27,7 +27,7 @@ def default_options(**kw):
              num_matching_frames=1, use_future_frame=False, pose_cnn=False, dc=False, distil=True, no_ens=False,
              temporal=False, main_temporal=False, dual_distil=False, learn_ens=False, no_ssim=False, loss_blc=False,
              disable_automasking=False, no_matching_augmentation=False, notadabins=False, fused_decoder=False, fused_encoder=False,
-             fused_pool=False, learning_rate=1e-4,
+             fused_pool=False, fused_adam=False, learning_rate=1e-4,
              scheduler_step_size=15, warmup_steps=0, decay_steps=1000, freeze_teacher_epoch=15,
              num_train_data=39810)  # KITTI eigen_zhou train split size (splits/eigen_zhou/train_files.txt)
     o.update(kw)
@@ -114,15 +114,21 @@ class TrainHarness:
             raise ValueError("TrainHarness: opt.temporal needs image_synthesis(inputs, outputs, scale) -> has_ins")
         self.model = networks.RepDepth(opt).to(self.device)
         self.params = [p for p in self.model.parameters() if p.requires_grad]
-        self.optimizer = torch.optim.Adam(self.params, opt.learning_rate)
+        # gradients of all trainable parameters as views of one buffer: one all-reduce per step
+        self.bucket = dp.FlatGradBucket(self.params, process_group, segments=exchange_segments)
+        self.fused_adam = bool(getattr(opt, "fused_adam", False))
+        if self.fused_adam:  # the same update as one HIP launch over the flat buffer, which it also zeroes (mal_amd.optim)
+            from .optim import FlatAdam
+            self.optimizer = FlatAdam(self.params, self.bucket, opt.learning_rate)
+        else:
+            self.optimizer = torch.optim.Adam(self.params, opt.learning_rate)
+        self._grads_zeroed = False  # fused_adam: the last optimizer step left the flat buffer zero
         if getattr(opt, "warmup_steps", 0):
             self.scheduler = WarmupStepLRScheduler(self.optimizer, 1e-7, opt.learning_rate, opt.warmup_steps, opt.decay_steps)
         else:
             self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, opt.scheduler_step_size, 0.1)
         self.tracker = DepthBinTracker(opt.min_depth)
         self.loss_blc = loss_utils.LossBalancing(2, opt.num_train_data, opt.batch_size) if opt.loss_blc else None
-        # gradients of all trainable parameters as views of one buffer: one all-reduce per step
-        self.bucket = dp.FlatGradBucket(self.params, process_group, segments=exchange_segments)
         self.step_count = 0
         self.issued_inside_backward = 0
 
@@ -151,13 +157,18 @@ class TrainHarness:
         mark = timer.mark if timer is not None else (lambda name: None)
         self.model.train()
         mark("start")
-        self.bucket.begin_step()
+        self.bucket.begin_step(zero=not self._grads_zeroed)
+        self._grads_zeroed = False
         outputs, losses = self.process_batch(inputs, self.step_count, timer)
         losses["loss"].backward()  # N>1: the bucket's pieces are all-reduced from inside it as they complete (dp.py)
         mark("loss_path_bwd+networks_bwd")
         self.issued_inside_backward = self.bucket.finish()
         mark("grad_all_reduce")
-        self.optimizer.step()
+        if self.fused_adam:
+            self.optimizer.step(zero_grad=True)
+            self._grads_zeroed = True
+        else:
+            self.optimizer.step()
         mark("adam")
         self.step_count += 1
         return losses
