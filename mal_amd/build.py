@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmal_hip.so")
 SOURCES = ["mal_api.hip", "mal_eval.hip", "mal_dyn_eval.hip", "mal_pass.hip", "mal_warp.hip", "mal_photo.hip", "mal_photo_march.hip", "mal_holes.hip", "mal_dyn.hip", "mal_match.hip", "mal_instances.hip", "mal_msda.hip", "mal_fwarp.hip", "mal_costvol.hip", "mal_epipolar.hip", "mal_pose.hip", "mal_march.hip", "mal_step.hip", "mal_step_ms.hip", "mal_dr_step.hip", "mal_glue.hip", "mal_bn.hip", "mal_pool.hip", "mal_adam.hip"]
-HEADERS = ["mal_common.h", "mal_device.h", "mal_march.h", "mal_pose.h", "mal_pairs.h", "mal_tail.h", "mal_eval_core.h", os.path.join("..", "..", "include", "mal_hip.h")]
+HEADERS = ["mal_common.h", "mal_device.h", "mal_march.h", "mal_pose.h", "mal_pairs.h", "mal_tail.h", "mal_eval_core.h", "mal_sample.h", os.path.join("..", "..", "include", "mal_hip.h")]
 # csrc/experiments/: formulations that lost their same-box A/Bs (LABBOOK.md) -- whole sources and the .inc halves the shipped
 # sources include under #ifdef MAL_EXPERIMENTS.  Not part of the product: compiled only with MAL_EXPERIMENTS=1 in the environment.
 EXPERIMENT_SOURCES = [os.path.join("experiments", "mal_tile2.hip")]

@@ -15,34 +15,47 @@ from . import _lib as L
 from . import ops
 
 
-def _run(current_feats, lookup_feats, relative_poses, K, invK, depth_bins, set_missing_to_max, want):
+# The input preparation of both routes, in the two halves between which the dynamic route handles its images and aug_mask
+# (so that each route reports its refusals in the order it always did).
+def _features(current_feats, lookup_feats):
+    """-> (cur, look, (B, F, C, h, w)): the feature shape check, then both maps as contiguous float32 device tensors"""
     B, C, h, w = current_feats.shape
     if lookup_feats.dim() != 5 or lookup_feats.shape[0] != B or tuple(lookup_feats.shape[2:]) != (C, h, w):
         raise L.MalError("lookup_feats must be (B,F,C,h,w) matching current_feats (B,C,h,w)")
     cur = ops._req(current_feats.detach(), "current_feats")
     look = ops._req(lookup_feats.detach(), "lookup_feats")
-    F_ = look.shape[1]
-    dev = cur.device
+    return cur, look, (B, look.shape[1], C, h, w)
+
+
+def _geometry(dev, depth_bins, relative_poses, K, invK, B, F_):
+    """-> (bins (D), poses (B,F,16), K (B,16), invK (B,16)) on the device"""
     bins = torch.as_tensor(depth_bins, dtype=torch.float32).to(dev).contiguous().reshape(-1)
+    poses = ops._req(relative_poses.detach().reshape(B, F_, 16).contiguous(), "relative_poses")
+    Kc, iKc = ops._req(K.detach().reshape(B, 16).contiguous(), "K"), ops._req(invK.detach().reshape(B, 16).contiguous(), "invK")
+    return bins, poses, Kc, iKc
+
+
+def _outputs(dev, B, D, h, w, want):
+    """(cost volume, missing, masked, lowest_cost, confidence): the volume always, the others where ``want`` asks."""
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    return (new(B, D, h, w), new(B, D, h, w) if want["missing"] else None, new(B, D, h, w) if want["masked"] else None,
+            new(B, h, w) if want["lowest"] else None, new(B, h, w) if want["confidence"] else None)
+
+
+def _run(current_feats, lookup_feats, relative_poses, K, invK, depth_bins, set_missing_to_max, want):
+    cur, look, (B, F_, C, h, w) = _features(current_feats, lookup_feats)
+    bins, poses, Kc, iKc = _geometry(cur.device, depth_bins, relative_poses, K, invK, B, F_)
     D = bins.numel()
     if L.load().mal_costvol_channel_last():  # first formulation (mal_set_option("costvol_impl", 0)): relayout
         cl = cur.permute(0, 2, 3, 1).contiguous()
         ll = look.permute(0, 1, 3, 4, 2).contiguous()
     else:                                    # default: the kernels read the encoder's own (B,C,h,w) layout
-        cl, ll = cur, ops._req(look, "lookup_feats")
-    poses = ops._req(relative_poses.detach().reshape(B, F_, 16).contiguous(), "relative_poses")
-    Kc, iKc = ops._req(K.detach().reshape(B, 16).contiguous(), "K"), ops._req(invK.detach().reshape(B, 16).contiguous(), "invK")
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    cv = new(B, D, h, w)
-    miss = new(B, D, h, w) if want["missing"] else None
-    masked = new(B, D, h, w) if want["masked"] else None
-    low = new(B, h, w) if want["lowest"] else None
-    conf = new(B, h, w) if want["confidence"] else None
+        cl, ll = cur, look
+    outs = _outputs(cur.device, B, D, h, w, want)
     p = ops._p
     L.check(L.load().mal_cost_volume(p(cl), p(ll), p(poses), p(Kc), p(iKc), p(bins), B, F_, C, D, h, w, 1e-7,
-                                     1 if set_missing_to_max else 0, p(cv), p(miss), p(masked), p(low), p(conf),
-                                     ops._stream()), "mal_cost_volume")
-    return cv, miss, masked, low, conf
+                                     1 if set_missing_to_max else 0, *[p(o) for o in outs], ops._stream()), "mal_cost_volume")
+    return outs
 
 
 def match_features(current_feats, lookup_feats, relative_poses, K, invK, depth_bins, set_missing_to_max=True):
@@ -67,12 +80,7 @@ def _run_dynamic(current_feats, lookup_feats, relative_poses, K, invK, lookup_im
     if int(pool_r) > 2 or int(pool_r) < 0:
         raise L.MalError("--cv_pool_radius %d: the pooled fill supports a radius of 0..2 (a wider window leaves the image "
                          "around the pixels that carry a cost)" % int(pool_r))
-    B, C, h, w = current_feats.shape
-    if lookup_feats.dim() != 5 or lookup_feats.shape[0] != B or tuple(lookup_feats.shape[2:]) != (C, h, w):
-        raise L.MalError("lookup_feats must be (B,F,C,h,w) matching current_feats (B,C,h,w)")
-    cur = ops._req(current_feats.detach(), "current_feats")
-    look = ops._req(lookup_feats.detach(), "lookup_feats")
-    F_ = look.shape[1]
+    cur, look, (B, F_, C, h, w) = _features(current_feats, lookup_feats)
     dev = cur.device
     occ = bool(set_1) or bool(pool)
     imgs, H, W = None, 0, 0
@@ -89,28 +97,21 @@ def _run_dynamic(current_feats, lookup_feats, relative_poses, K, invK, lookup_im
     if aug_mask is not None:
         aug = ops._req(aug_mask.detach(), "aug_mask")
         aug = aug.reshape(B, -1)[:, 0].contiguous()  # upstream reads aug_mask[b][0][0][0] (:192)
-    bins = torch.as_tensor(depth_bins, dtype=torch.float32).to(dev).contiguous().reshape(-1)
+    bins, poses, Kc, iKc = _geometry(dev, depth_bins, relative_poses, K, invK, B, F_)
     D = bins.numel()
-    poses = ops._req(relative_poses.detach().reshape(B, F_, 16).contiguous(), "relative_poses")
-    Kc, iKc = ops._req(K.detach().reshape(B, 16).contiguous(), "K"), ops._req(invK.detach().reshape(B, 16).contiguous(), "invK")
     lib = L.load()
     ws = None
     if occ:
         need = lib.mal_cost_volume_dyn_workspace_bytes(B, F_, D, h, w)
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    cv = new(B, D, h, w)
-    miss = new(B, D, h, w) if want["missing"] else None
-    masked = new(B, D, h, w) if want["masked"] else None
-    low = new(B, h, w) if want["lowest"] else None
-    conf = new(B, h, w) if want["confidence"] else None
+    outs = _outputs(dev, B, D, h, w, want)
     p = ops._p
     L.check(lib.mal_cost_volume_dyn(p(cur), p(look), p(poses), p(Kc), p(iKc), p(bins), B, F_, C, D, h, w, 1e-7,
                                     1 if set_missing_to_max else 0, p(imgs), H, W, p(aug), int(bool(cv_min)),
-                                    int(bool(set_1)), int(bool(pool)), int(pool_r), float(pool_th), p(cv), p(miss), p(masked),
-                                    p(low), p(conf), p(ws), ws.numel() if ws is not None else 0, ops._stream()),
+                                    int(bool(set_1)), int(bool(pool)), int(pool_r), float(pool_th), *[p(o) for o in outs],
+                                    p(ws), ws.numel() if ws is not None else 0, ops._stream()),
             "mal_cost_volume_dyn")
-    return cv, miss, masked, low, conf
+    return outs
 
 
 def match_features_dynamic(current_feats, lookup_feats, relative_poses, K, invK, lookup_images, depth_bins, cv_min=True,

@@ -19,6 +19,7 @@
 //                          of the first minimum with zeros read as 100 (:303-307), volume x confidence (:311).
 #include "mal_common.h"
 #include "mal_device.h"
+#include "mal_sample.h"
 
 namespace mal {
 
@@ -40,8 +41,6 @@ struct CostVolParams {
 
 struct TapSet { int o[4]; float w[4]; float edge; };
 
-// the reference's chain for one (pixel, depth): layers.py:163-168 (X = depth * ray), :184-199 (project),
-// grid_sample's unnormalise with zeros padding, resnet_encoder.py:199-205 (border mask on the sampling position)
 // pix_locs of one (pixel, depth): X = depth * ray (layers.py:163-168), project and normalise (:184-199).  The one place this
 // chain is written: the feature taps below and the occlusion mask of the DynamicDepth variant sample at the same position.
 MAL_DEV void grid_position(const float* P, const float* ray, float depth, float eps, int w, int h, float& gx, float& gy) {
@@ -59,6 +58,8 @@ MAL_DEV void grid_position(const float* P, const float* ray, float depth, float 
   gy = (div_(v, (float)(h - 1)) - 0.5f) * 2.0f;
 }
 
+// the reference's chain for one (pixel, depth): grid_position, grid_sample's unnormalise (align_corners=True), the border mask
+// of resnet_encoder.py:199-205 on the sampling position, and the zero-padded taps of mal_sample.h (element offsets)
 MAL_DEV TapSet taps_for(const float* P, const float* ray, float depth, float eps, int w, int h) {
   TapSet t;
   float gx, gy;
@@ -67,19 +68,9 @@ MAL_DEV TapSet taps_for(const float* P, const float* ray, float depth, float eps
   const float ix = (gx + 1.0f) * (wm1 * 0.5f), iy = (gy + 1.0f) * (hm1 * 0.5f);
   const float xv = (gx / 2.0f + 0.5f) * wm1, yv = (gy / 2.0f + 0.5f) * hm1;
   t.edge = (xv >= 2.0f && xv <= (float)(w - 2) && yv >= 2.0f && yv <= (float)(h - 2)) ? 1.0f : 0.0f;
-  const float x0f = floorf(ix), y0f = floorf(iy);
-  const float tx = ix - x0f, ex = 1.0f - tx, ty = iy - y0f, ey = 1.0f - ty;
-  // keep the int conversion defined for wild projections: such taps are outside anyway
-  const float xc = fminf(fmaxf(x0f, -2.0f), (float)w + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)h + 1.0f);
-  const int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
-  const bool wild = !(x0f == xc && y0f == yc);  // also true for NaN
-  const bool vx0 = x0 >= 0 && x0 < w, vx1 = x1 >= 0 && x1 < w, vy0 = y0 >= 0 && y0 < h, vy1 = y1 >= 0 && y1 < h;
-  const int cx0 = min(max(x0, 0), w - 1), cx1 = min(max(x1, 0), w - 1), cy0 = min(max(y0, 0), h - 1), cy1 = min(max(y1, 0), h - 1);
-  t.o[0] = cy0 * w + cx0; t.o[1] = cy0 * w + cx1; t.o[2] = cy1 * w + cx0; t.o[3] = cy1 * w + cx1;
-  t.w[0] = (!wild && vx0 && vy0) ? ey * ex : 0.f;
-  t.w[1] = (!wild && vx1 && vy0) ? ey * tx : 0.f;
-  t.w[2] = (!wild && vx0 && vy1) ? ty * ex : 0.f;
-  t.w[3] = (!wild && vx1 && vy1) ? ty * tx : 0.f;
+  const Corners c = corners_of(ix, iy, w, h);
+  for (int k = 0; k < 4; ++k) t.o[k] = c.o[k];
+  tap_weights(c, frac_one_minus(ix, iy, c), t.w);
   return t;
 }
 
@@ -102,6 +93,20 @@ MAL_DEV float wave_sum_dpp(float v) {
 MAL_DEV float bcast(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
 MAL_DEV int bcasti(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
+MAL_DEV bool frame_missing(const float* T) {  // an all-zero pose is a missing lookup frame (:176-178); uniform per (b, f)
+  float tsum = 0.f;
+  for (int i = 0; i < 16; ++i) tsum += T[i];
+  return tsum == 0.f;
+}
+
+MAL_DEV bool inner_pixel(int x, int y, int w, int h) { return y >= 2 && y < h - 2 && x >= 2 && x < w - 2; }  // resnet_encoder.py:208-210
+
+// the sample's inverse intrinsics (kept: the pooled fill derives its neighbours' rays from them) and the pixel's ray
+MAL_DEV void pixel_ray(const CostVolParams& p, int b, int x, int y, float ik[9], float ray[3]) {
+  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
+  ray_of(ik, (float)x, (float)y, ray);
+}
+
 __global__ __launch_bounds__(256) void costvol_match_kernel(CostVolParams p) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int h = p.h, w = p.w, hw = h * w;
@@ -110,22 +115,18 @@ __global__ __launch_bounds__(256) void costvol_match_kernel(CostVolParams p) {
   const int pix = y * w + xg;
   const int rounds = (p.D + 63) / 64;
   float* out = p.cost + (size_t)b * p.D * hw + pix;
-  const bool inner = y >= 2 && y < h - 2 && xg >= 2 && xg < w - 2;  // resnet_encoder.py:208-210
-  if (!inner) {  // every difference is masked: cost 0 / (0 + 1e-7) = 0
+  if (!inner_pixel(xg, y, w, h)) {  // every difference is masked: cost 0 / (0 + 1e-7) = 0
     for (int k = 0; k < rounds; ++k)
       if (k * 64 + lane < p.D) out[(size_t)(k * 64 + lane) * hw] = 0.f;
     return;
   }
   const float curv = p.cur[((size_t)b * hw + pix) * kCvC + lane];
   float ray[3], ik[9];
-  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
-  ray_of(ik, (float)xg, (float)y, ray);
+  pixel_ray(p, b, xg, y, ik, ray);
   float acc[4] = {0.f, 0.f, 0.f, 0.f}, cnt[4] = {0.f, 0.f, 0.f, 0.f};  // bins lane, lane+64, ... (D <= 256)
   for (int f = 0; f < p.F; ++f) {
     const float* T = p.poses + ((size_t)b * p.F + f) * 16;
-    float tsum = 0.f;
-    for (int i = 0; i < 16; ++i) tsum += T[i];
-    if (tsum == 0.f) continue;  // a missing lookup frame (:176-178); wave-uniform
+    if (frame_missing(T)) continue;
     float P[12];
     compose_P(p.K + b * 16, T, P);
     const float* lf = p.look + (((size_t)b * p.F + f) * hw) * kCvC + lane;
@@ -138,12 +139,8 @@ __global__ __launch_bounds__(256) void costvol_match_kernel(CostVolParams p) {
       for (int j = 0; j < nb; ++j) {                                                   // phase 2: lane = channel
         if (bcast(t.edge, j) == 0.f) continue;  // masked out (wave-uniform): the difference would be multiplied by 0
         const int o0 = bcasti(t.o[0], j), o1 = bcasti(t.o[1], j), o2 = bcasti(t.o[2], j), o3 = bcasti(t.o[3], j);
-        const float w0 = bcast(t.w[0], j), w1 = bcast(t.w[1], j), w2 = bcast(t.w[2], j), w3 = bcast(t.w[3], j);
-        const float a = lf[(size_t)o0 * kCvC], bb = lf[(size_t)o1 * kCvC], c = lf[(size_t)o2 * kCvC], d = lf[(size_t)o3 * kCvC];
-        float o = a * w0;
-        o = fma_(bb, w1, o);
-        o = fma_(c, w2, o);
-        o = fma_(d, w3, o);
+        const float wj[4] = {bcast(t.w[0], j), bcast(t.w[1], j), bcast(t.w[2], j), bcast(t.w[3], j)};
+        const float o = blend4(lf[(size_t)o0 * kCvC], lf[(size_t)o1 * kCvC], lf[(size_t)o2 * kCvC], lf[(size_t)o3 * kCvC], wj);
         const float s = wave_sum_dpp(fabsf(o - curv));        // lane 63 holds the sum
         const float diff = bcast(s, 63) * (1.0f / (float)kCvC) * bcast(t.edge, j);
         if (lane == j) { acc[k] += diff; cnt[k] += diff > 0.f ? 1.0f : 0.f; }
@@ -167,9 +164,71 @@ __global__ __launch_bounds__(256) void costvol_match_kernel(CostVolParams p) {
 // slower too (0.58 ms).
 constexpr int kCvG = 6;
 
-// costvol_match_dyn_kernel below repeats this kernel's setup, tap and channel loops for DynamicDepth's variant and must equal it
-// bit for bit with its options off (tests/test_gpu_dyn_costvol.py holds that): a change here is a change there.
-__global__ __launch_bounds__(256) void costvol_match_px_kernel(CostVolParams p) {
+// ---- the parts of a lane = pixel matching kernel, written once: costvol_match_px_kernel and costvol_match_dyn_kernel are
+// match_px below and nothing else; costvol_match_pool_kernel (an LDS tile, thread = pixel) uses them around its tile code.
+// One frame's taps of a pixel for its kCvG bins: byte offsets, weights, the border mask (0 outside the inner region) and
+// zeroed channel sums.  Returns whether any bin of this lane carries a cost.
+MAL_DEV bool frame_taps(const CostVolParams& p, const float* P, const float* ray, int d0, bool inner, unsigned off[kCvG][4],
+                        float wt[kCvG][4], float edge[kCvG], float sum[kCvG]) {
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j) {
+    const TapSet t = taps_for(P, ray, p.bins[min(d0 + j, p.D - 1)], p.eps, p.w, p.h);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { off[j][k] = (unsigned)t.o[k] * 4u; wt[j][k] = t.w[k]; }
+    edge[j] = inner ? t.edge : 0.f;
+    sum[j] = 0.f;
+    any = any || edge[j] != 0.f;
+  }
+  return any;
+}
+
+// the plain loop: sum over the 64 channel planes of |warped lookup - current| for the pixel's kCvG bins
+MAL_DEV void channel_sums(const float* lf, const float* cf, int hw, int pix, const unsigned (*off)[4], const float (*wt)[4],
+                          float sum[kCvG]) {
+  for (int ch = 0; ch < kCvC; ++ch) {
+    const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
+    const float cv = cf[(size_t)ch * hw + pix];
+#pragma unroll
+    for (int j = 0; j < kCvG; ++j) sum[j] += fabsf(plane_sample(pl, off[j], wt[j]) - cv);
+  }
+}
+
+// Frames fuse by the mean over the hits (ManyDepth; DynamicDepth without cv_min) or by minimum (cv_min, :226: a difference
+// of 0 reads as 1 = no change, and an untouched 1 is stored as 0).
+template <bool CVMIN>
+MAL_DEV void fuse_init(float acc[kCvG], float cnt[kCvG]) {
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j) { acc[j] = CVMIN ? 1.f : 0.f; cnt[j] = 0.f; }
+}
+template <bool CVMIN>
+MAL_DEV void fuse_frame(const float sum[kCvG], const float edge[kCvG], float acc[kCvG], float cnt[kCvG]) {
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j) {
+    const float diff = sum[j] * (1.0f / (float)kCvC) * edge[j];
+    if (CVMIN) {
+      const float dm = diff == 0.f ? 1.0f : diff;
+      acc[j] = (dm < acc[j] || dm != dm) ? dm : acc[j];  // torch.minimum
+    } else {
+      acc[j] += diff;
+      cnt[j] += diff > 0.f ? 1.0f : 0.f;
+    }
+  }
+}
+template <bool CVMIN>
+MAL_DEV void store_bins(const CostVolParams& p, int b, int pix, int d0, bool live, const float acc[kCvG], const float cnt[kCvG]) {
+  const int hw = p.h * p.w;
+  float* out = p.cost + (size_t)b * p.D * hw + pix;
+#pragma unroll
+  for (int j = 0; j < kCvG; ++j)  // mean: 0 / 1e-7 = 0 outside the inner region
+    if (live && d0 + j < p.D) out[(size_t)(d0 + j) * hw] =CVMIN ? (acc[j] == 1.0f ? 0.f : acc[j]) : div_(acc[j], cnt[j] + 1e-7f);
+}
+
+// The matching loop of a wavefront that owns 64 consecutive pixels and kCvG bins.  OCC = false: the plain loop and nothing
+// else.  OCC = true: DynamicDepth's set_1 -- only in a wavefront that holds a masked cell (byte of m) with a live border mask,
+// the masked cells take |1 - current| per channel; aug (nullable) switches that off per sample, read here.
+template <bool OCC, bool CVMIN>
+MAL_DEV void match_px(const CostVolParams& p, const unsigned char* m, const float* aug) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int h = p.h, w = p.w, hw = h * w;
   const int pix0 = (blockIdx.x * 4 + wv) * 64, grp = blockIdx.y, b = blockIdx.z;
@@ -177,62 +236,47 @@ __global__ __launch_bounds__(256) void costvol_match_px_kernel(CostVolParams p) 
   const bool live = pix0 + lane < hw;
   const int pix = min(pix0 + lane, hw - 1);
   const int y = pix / w, x = pix - y * w;
-  const bool inner = y >= 2 && y < h - 2 && x >= 2 && x < w - 2;  // resnet_encoder.py:208-210
+  const bool inner = inner_pixel(x, y, w, h);
   const int d0 = grp * kCvG;
   float ray[3], ik[9];
-  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
-  ray_of(ik, (float)x, (float)y, ray);
+  pixel_ray(p, b, x, y, ik, ray);
   float acc[kCvG], cnt[kCvG];
-#pragma unroll
-  for (int j = 0; j < kCvG; ++j) { acc[j] = 0.f; cnt[j] = 0.f; }
+  fuse_init<CVMIN>(acc, cnt);
   const float* cf = p.cur + (size_t)b * kCvC * hw;
+  const bool occ_on = OCC && !(aug && aug[b] != 0.f);  // :192, on the device; wave-uniform
   for (int f = 0; f < p.F; ++f) {
     const float* T = p.poses + ((size_t)b * p.F + f) * 16;
-    float tsum = 0.f;
-    for (int i = 0; i < 16; ++i) tsum += T[i];
-    if (tsum == 0.f) continue;  // a missing lookup frame (:176-178); wave-uniform
+    if (frame_missing(T)) continue;
     float P[12];
     compose_P(p.K + b * 16, T, P);
     unsigned off[kCvG][4];
     float wt[kCvG][4], edge[kCvG], sum[kCvG];
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < kCvG; ++j) {
-      const TapSet t = taps_for(P, ray, p.bins[min(d0 + j, p.D - 1)], p.eps, w, h);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { off[j][k] = (unsigned)t.o[k] * 4u; wt[j][k] = t.w[k]; }
-      edge[j] = inner ? t.edge : 0.f;
-      sum[j] = 0.f;
-      any = any || edge[j] != 0.f;
-    }
-    if (__ballot(any) == 0ull) continue;  // every (pixel, bin) of this wave is masked out: all differences are x 0
-    const float* lf = p.look + ((size_t)b * p.F + f) * kCvC * hw;
-    for (int ch = 0; ch < kCvC; ++ch) {
-      const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
-      const float cv = cf[(size_t)ch * hw + pix];
+    const bool any = frame_taps(p, P, ray, d0, inner, off, wt, edge, sum);
+    if (__ballot(any) == 0ull) continue;  // every (pixel, bin) of this wave is masked out: diffs 0, which cv_min reads as no change
+    channel_sums(p.look + ((size_t)b * p.F + f) * kCvC * hw, cf, hw, pix, off, wt, sum);
+    if (OCC && occ_on) {
+      // a masked cell whose border mask is 0 keeps a difference of 0 whatever it samples
+      const unsigned char* mf = m + ((size_t)b * p.F + f) * p.D * hw;
+      bool need[kCvG], anyneed = false;
 #pragma unroll
       for (int j = 0; j < kCvG; ++j) {
-        const float a = *reinterpret_cast<const float*>(pl + off[j][0]), bb = *reinterpret_cast<const float*>(pl + off[j][1]);
-        const float c = *reinterpret_cast<const float*>(pl + off[j][2]), d = *reinterpret_cast<const float*>(pl + off[j][3]);
-        float o = a * wt[j][0];
-        o = fma_(bb, wt[j][1], o);
-        o = fma_(c, wt[j][2], o);
-        o = fma_(d, wt[j][3], o);
-        sum[j] += fabsf(o - cv);
+        need[j] = d0 + j < p.D && edge[j] != 0.f && mf[(size_t)(d0 + j) * hw + pix] != 0;
+        anyneed = anyneed || need[j];
+      }
+      if (__ballot(anyneed) != 0ull) {  // set_1 (the pooled fill has a kernel of its own)
+        float s1 = 0.f;
+        for (int ch = 0; ch < kCvC; ++ch) s1 += fabsf(1.0f - cf[(size_t)ch * hw + pix]);
+#pragma unroll
+        for (int j = 0; j < kCvG; ++j) sum[j] = need[j] ? s1 : sum[j];
       }
     }
-#pragma unroll
-    for (int j = 0; j < kCvG; ++j) {
-      const float diff = sum[j] * (1.0f / (float)kCvC) * edge[j];
-      acc[j] += diff;
-      cnt[j] += diff > 0.f ? 1.0f : 0.f;
-    }
+    fuse_frame<CVMIN>(sum, edge, acc, cnt);
   }
-  float* out = p.cost + (size_t)b * p.D * hw + pix;
-#pragma unroll
-  for (int j = 0; j < kCvG; ++j)
-    if (live && d0 + j < p.D) out[(size_t)(d0 + j) * hw] = div_(acc[j], cnt[j] + 1e-7f);  // 0 / 1e-7 = 0 outside the inner region
+  store_bins<CVMIN>(p, b, pix, d0, live, acc, cnt);
 }
+
+__global__ __launch_bounds__(256) void costvol_match_px_kernel(CostVolParams p) { match_px<false, false>(p, nullptr, nullptr); }
+
 
 // 64 pixels per workgroup, the bins split over its four wavefronts (lane = pixel: every access is a coalesced row
 // piece of one bin plane); the pixel's maximum / hit count / first minimum are combined through LDS in bin order
@@ -293,10 +337,11 @@ __global__ __launch_bounds__(256) void costvol_finish_kernel(CostVolParams p) {
 //                             image of FLAT index b, upstream's indexing, not b*F+f -- at the cell's sampling position,
 //                             compared strictly with pool_th; one byte per cell, every pixel (the pool reads border pixels
 //                             as neighbours).  Skipped for augmented samples and missing frames, whose bytes are never read.
-//   costvol_match_dyn_kernel  options off and set_1: costvol_match_px_kernel's loop, then -- only in a wavefront that holds a
-//                             masked cell with a live border mask -- the masked cells take |1 - current| per channel.
+//   costvol_match_dyn_kernel  options off and set_1: match_px above, the very body of costvol_match_px_kernel; with set_1 -- only
+//                             in a wavefront that holds a masked cell with a live border mask -- the masked cells take
+//                             |1 - current| per channel.
 //   costvol_match_pool_kernel pool: an LDS tile of 8 x 32 pixels x 6 bins with a halo of r (described at the kernel); a
-//                             neighbour's sample comes from taps_for with ITS ray and bin and from tap_sample, the function
+//                             neighbour's sample comes from taps_for with ITS ray and bin and from plane_sample, the function
 //                             the centre uses, so the maximum is exact and does not depend on the tiling.
 //                             Frames fuse by minimum (cv_min) or by the mean over the hits, in both.
 //   costvol_finish_kernel     unchanged.
@@ -325,12 +370,6 @@ __global__ __launch_bounds__(256) void costvol_occ_image_kernel(CostVolDynParams
   q.occ[(size_t)n * kOccH * kOccW + i] = s < 0.15f ? 1 : 0;
 }
 
-MAL_DEV bool frame_missing(const float* T) {  // :185, in the order of the plain kernel
-  float tsum = 0.f;
-  for (int i = 0; i < 16; ++i) tsum += T[i];
-  return tsum == 0.f;
-}
-
 __global__ __launch_bounds__(256) void costvol_occ_mask_kernel(CostVolDynParams q) {
   const CostVolParams& p = q.cv;
   const int h = p.h, w = p.w, hw = h * w;
@@ -341,126 +380,35 @@ __global__ __launch_bounds__(256) void costvol_occ_mask_kernel(CostVolDynParams 
   if (frame_missing(T)) return;
   const int y = pix / w, x = pix - y * w;
   float ray[3], ik[9], P[12];
-  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
-  ray_of(ik, (float)x, (float)y, ray);
+  pixel_ray(p, b, x, y, ik, ray);
   compose_P(p.K + b * 16, T, P);
   float gx, gy;
   grid_position(P, ray, p.bins[d], p.eps, w, h, gx, gy);  // the position the feature taps are built from
   // grid_sample on the 48x128 image: zeros padding, bilinear, align_corners=True
   const float ix = ((gx + 1.0f) / 2.0f) * (float)(kOccW - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(kOccH - 1);
-  const float x0f = floorf(ix), y0f = floorf(iy);
-  const float tx = ix - x0f, ex = 1.0f - tx, ty = iy - y0f, ey = 1.0f - ty;
-  const float xc = fminf(fmaxf(x0f, -2.0f), (float)kOccW + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)kOccH + 1.0f);
-  const bool wild = !(x0f == xc && y0f == yc);  // also true for NaN: every tap outside
-  const int x0 = (int)xc, y0 = (int)yc;
+  const Corners c = corners_of(ix, iy, kOccW, kOccH);
+  const Frac fr = frac_one_minus(ix, iy, c);
   const unsigned char* oc = q.occ + (size_t)b * kOccH * kOccW;  // occ[b], not occ[b*F+f] (:194)
   float val = 0.f;
-  if (!wild) {
-    auto tap = [&](int yy, int xx) { return (yy >= 0 && yy < kOccH && xx >= 0 && xx < kOccW) ? (float)oc[yy * kOccW + xx] : 0.f; };
-    val = tap(y0, x0) * (ex * ey);
-    val += tap(y0, x0 + 1) * (tx * ey);
-    val += tap(y0 + 1, x0) * (ex * ty);
-    val += tap(y0 + 1, x0 + 1) * (tx * ty);
+  if (!c.wild) {  // byte taps, unzeroed weights and plain adds: this sample keeps its own arithmetic
+    auto tap = [&](int k) { return c.v[k] ? (float)oc[c.o[k]] : 0.f; };
+    val = tap(0) * (fr.ex * fr.ey);
+    val += tap(1) * (fr.tx * fr.ey);
+    val += tap(2) * (fr.ex * fr.ty);
+    val += tap(3) * (fr.tx * fr.ty);
   }
   q.m[((size_t)bf * p.D + d) * hw + pix] = val > q.pool_th ? 1 : 0;
 }
 
-// one bilinear sample of a feature plane: the multiply and the three fmas of costvol_match_px_kernel
-MAL_DEV float tap_sample(const char* pl, const unsigned off[4], const float wt[4]) {
-  const float a = *reinterpret_cast<const float*>(pl + off[0]), bb = *reinterpret_cast<const float*>(pl + off[1]);
-  const float c = *reinterpret_cast<const float*>(pl + off[2]), d = *reinterpret_cast<const float*>(pl + off[3]);
-  float o = a * wt[0];
-  o = fma_(bb, wt[1], o);
-  o = fma_(c, wt[2], o);
-  o = fma_(d, wt[3], o);
-  return o;
-}
-
-// OCC = false: options off, the plain loop and nothing else.  OCC = true: set_1; aug_mask is read here.
 template <bool OCC, bool CVMIN>
-__global__ __launch_bounds__(256) void costvol_match_dyn_kernel(CostVolDynParams q) {
-  const CostVolParams& p = q.cv;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int h = p.h, w = p.w, hw = h * w;
-  const int pix0 = (blockIdx.x * 4 + wv) * 64, grp = blockIdx.y, b = blockIdx.z;
-  if (pix0 >= hw) return;
-  const bool live = pix0 + lane < hw;
-  const int pix = min(pix0 + lane, hw - 1);
-  const int y = pix / w, x = pix - y * w;
-  const bool inner = y >= 2 && y < h - 2 && x >= 2 && x < w - 2;
-  const int d0 = grp * kCvG;
-  float ray[3], ik[9];
-  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
-  ray_of(ik, (float)x, (float)y, ray);
-  float acc[kCvG], cnt[kCvG];
-#pragma unroll
-  for (int j = 0; j < kCvG; ++j) { acc[j] = CVMIN ? 1.f : 0.f; cnt[j] = 0.f; }
-  const float* cf = p.cur + (size_t)b * kCvC * hw;
-  const bool occ_on = OCC && !(q.aug && q.aug[b] != 0.f);  // :192, on the device; wave-uniform
-  for (int f = 0; f < p.F; ++f) {
-    const float* T = p.poses + ((size_t)b * p.F + f) * 16;
-    if (frame_missing(T)) continue;
-    float P[12];
-    compose_P(p.K + b * 16, T, P);
-    unsigned off[kCvG][4];
-    float wt[kCvG][4], edge[kCvG], sum[kCvG];
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < kCvG; ++j) {
-      const TapSet t = taps_for(P, ray, p.bins[min(d0 + j, p.D - 1)], p.eps, w, h);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { off[j][k] = (unsigned)t.o[k] * 4u; wt[j][k] = t.w[k]; }
-      edge[j] = inner ? t.edge : 0.f;
-      sum[j] = 0.f;
-      any = any || edge[j] != 0.f;
-    }
-    if (__ballot(any) == 0ull) continue;  // all differences are x 0: diffs 0, which cv_min reads as 1 = no change
-    const float* lf = p.look + ((size_t)b * p.F + f) * kCvC * hw;
-    for (int ch = 0; ch < kCvC; ++ch) {
-      const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
-      const float cv = cf[(size_t)ch * hw + pix];
-#pragma unroll
-      for (int j = 0; j < kCvG; ++j) sum[j] += fabsf(tap_sample(pl, off[j], wt[j]) - cv);
-    }
-    if (OCC && occ_on) {
-      // a masked cell whose border mask is 0 keeps a difference of 0 whatever it samples
-      const unsigned char* mf = q.m + ((size_t)b * p.F + f) * p.D * hw;
-      bool need[kCvG], anyneed = false;
-#pragma unroll
-      for (int j = 0; j < kCvG; ++j) {
-        need[j] = d0 + j < p.D && edge[j] != 0.f && mf[(size_t)(d0 + j) * hw + pix] != 0;
-        anyneed = anyneed || need[j];
-      }
-      if (__ballot(anyneed) != 0ull) {  // set_1 (the pooled fill has a kernel of its own)
-        float s1 = 0.f;
-        for (int ch = 0; ch < kCvC; ++ch) s1 += fabsf(1.0f - cf[(size_t)ch * hw + pix]);
-#pragma unroll
-        for (int j = 0; j < kCvG; ++j) sum[j] = need[j] ? s1 : sum[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kCvG; ++j) {
-      const float diff = sum[j] * (1.0f / (float)kCvC) * edge[j];
-      if (CVMIN) {
-        const float dm = diff == 0.f ? 1.0f : diff;            // :226
-        acc[j] = (dm < acc[j] || dm != dm) ? dm : acc[j];      // torch.minimum
-      } else {
-        acc[j] += diff;
-        cnt[j] += diff > 0.f ? 1.0f : 0.f;
-      }
-    }
-  }
-  float* out = p.cost + (size_t)b * p.D * hw + pix;
-#pragma unroll
-  for (int j = 0; j < kCvG; ++j)
-    if (live && d0 + j < p.D) out[(size_t)(d0 + j) * hw] = CVMIN ? (acc[j] == 1.0f ? 0.f : acc[j]) : div_(acc[j], cnt[j] + 1e-7f);
-}
+__global__ __launch_bounds__(256) void costvol_match_dyn_kernel(CostVolDynParams q) { match_px<OCC, CVMIN>(q.cv, q.m, q.aug); }
+
 
 // The pooled fill as an LDS tile.  A workgroup owns 8 x 32 pixels (thread = pixel) and kCvG bins.  Options and frames are
 // tested workgroup-uniformly; a tile without a masked cell that carries a cost runs the plain loop.  Otherwise the tile plus a
 // halo of R in bin, y and x is spread over the threads (cell i of the haloed tile belongs to thread i mod 256): each thread
 // derives ITS cells' taps once per frame with taps_for from the cell's own ray and bin, and per channel writes their samples
-// -- tap_sample, the function of the plain loop; 0 for masked cells and for cells outside the volume, which is what they
+// -- plane_sample, the function of the plain loop; 0 for masked cells and for cells outside the volume, which is what they
 // contribute to a maximum that already holds the masked centre's 0 -- into one of two LDS planes; after one barrier every
 // thread takes, for each of its own cells, the plane's value (unmasked: the very sample the plain loop computes), or the
 // maximum over the (2R+1)^3 window (masked), or 0 outright when the whole window is masked (found once per frame from the
@@ -482,13 +430,11 @@ __global__ __launch_bounds__(256) void costvol_match_pool_kernel(CostVolDynParam
   const int grp = blockIdx.y, b = blockIdx.z, d0 = grp * kCvG;
   const bool live = ty0 + ly < h && tx0 + lx < w;
   const int y = min(ty0 + ly, h - 1), x = min(tx0 + lx, w - 1), pix = y * w + x;
-  const bool inner = live && y >= 2 && y < h - 2 && x >= 2 && x < w - 2;
+  const bool inner = live && inner_pixel(x, y, w, h);
   float ray[3], ik[9];
-  for (int e = 0; e < 9; ++e) ik[e] = p.invK[b * 16 + (e / 3) * 4 + (e % 3)];
-  ray_of(ik, (float)x, (float)y, ray);
+  pixel_ray(p, b, x, y, ik, ray);
   float acc[kCvG], cnt[kCvG];
-#pragma unroll
-  for (int j = 0; j < kCvG; ++j) { acc[j] = CVMIN ? 1.f : 0.f; cnt[j] = 0.f; }
+  fuse_init<CVMIN>(acc, cnt);
   const float* cf = p.cur + (size_t)b * kCvC * hw;
   const bool occ_on = !(q.aug && q.aug[b] != 0.f);  // :192, on the device; workgroup-uniform
   for (int f = 0; f < p.F; ++f) {
@@ -556,12 +502,7 @@ __global__ __launch_bounds__(256) void costvol_match_pool_kernel(CostVolDynParam
       if (!valid) zero |= 1u << k;
     }
     if (!tile_need) {
-      for (int ch = 0; ch < kCvC; ++ch) {
-        const char* pl = reinterpret_cast<const char*>(lf + (size_t)ch * hw);
-        const float cv = cf[(size_t)ch * hw + pix];
-#pragma unroll
-        for (int j = 0; j < kCvG; ++j) sum[j] += fabsf(tap_sample(pl, coff[j], cwt[j]) - cv);
-      }
+      channel_sums(lf, cf, hw, pix, coff, cwt, sum);  // NC >= kCvG: cells 0..kCvG-1 are this thread's own
     } else {
       for (int ch = 0; ch < kCvC; ++ch) {
         float* buf = s_v[ch & 1];
@@ -569,7 +510,7 @@ __global__ __launch_bounds__(256) void costvol_match_pool_kernel(CostVolDynParam
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
           const int i = tid + k * 256;
-          const float v = tap_sample(pl, coff[k], cwt[k]);
+          const float v = plane_sample(pl, coff[k], cwt[k]);
           if (i < NCELL) buf[i] = ((zero >> k) & 1u) ? 0.f : v;
         }
         __syncthreads();
@@ -609,22 +550,9 @@ __global__ __launch_bounds__(256) void costvol_match_pool_kernel(CostVolDynParam
         }
       }
     }
-#pragma unroll
-    for (int j = 0; j < kCvG; ++j) {
-      const float diff = sum[j] * (1.0f / (float)kCvC) * edge[j];
-      if (CVMIN) {
-        const float dm = diff == 0.f ? 1.0f : diff;
-        acc[j] = (dm < acc[j] || dm != dm) ? dm : acc[j];
-      } else {
-        acc[j] += diff;
-        cnt[j] += diff > 0.f ? 1.0f : 0.f;
-      }
-    }
+    fuse_frame<CVMIN>(sum, edge, acc, cnt);
   }
-  float* out = p.cost + (size_t)b * p.D * hw + pix;
-#pragma unroll
-  for (int j = 0; j < kCvG; ++j)
-    if (live && d0 + j < p.D) out[(size_t)(d0 + j) * hw] = CVMIN ? (acc[j] == 1.0f ? 0.f : acc[j]) : div_(acc[j], cnt[j] + 1e-7f);
+  store_bins<CVMIN>(p, b, pix, d0, live, acc, cnt);
 }
 
 }  // namespace mal
@@ -635,19 +563,36 @@ namespace mal { opt_t g_costvol_impl{1}; }  // 1 = planar features, lane = pixel
 
 extern "C" int mal_costvol_channel_last(void) { return g_costvol_impl == 0; }
 
-extern "C" int mal_cost_volume(const float* current_feats, const float* lookup_feats, const float* poses, const float* K,
-                               const float* inv_K, const float* depth_bins, int B, int F, int C, int D, int h, int w,
-                               float eps, int set_missing_to_max, float* cost_volume, float* missing_mask,
-                               float* masked_cost_volume, float* lowest_cost, float* confidence_mask, void* stream) {
+// what both entry points refuse as a shape, and the record both fill
+static int costvol_shape_status(int B, int F, int C, int D, int h, int w) {
   if (B <= 0 || F <= 0 || D <= 0 || h < 5 || w < 5) return MAL_ESHAPE;
   if (C != kCvC || D > 256) return MAL_ESHAPE;  // lanes = channels; four bins per lane at most
   if ((double)B * D * h * w > 2.0e9 / 4 || (double)B * F * h * w * C > 2.0e9 / 4) return MAL_ESHAPE;
-  if (!current_feats || !lookup_feats || !poses || !K || !inv_K || !depth_bins || !cost_volume) return MAL_EINVAL;
+  return MAL_OK;
+}
+
+static CostVolParams costvol_params(const float* current_feats, const float* lookup_feats, const float* poses, const float* K,
+                                    const float* inv_K, const float* depth_bins, int B, int F, int D, int h, int w, float eps,
+                                    int set_missing_to_max, float* cost_volume, float* missing_mask, float* masked_cost_volume,
+                                    float* lowest_cost, float* confidence_mask) {
   CostVolParams p = {};
   p.cur = current_feats; p.look = lookup_feats; p.poses = poses; p.K = K; p.invK = inv_K; p.bins = depth_bins;
   p.B = B; p.F = F; p.D = D; p.h = h; p.w = w; p.eps = eps; p.set_missing_to_max = set_missing_to_max;
   p.cost = cost_volume; p.missing = missing_mask; p.masked = masked_cost_volume; p.lowest_cost = lowest_cost;
   p.confidence = confidence_mask;
+  return p;
+}
+
+extern "C" int mal_cost_volume(const float* current_feats, const float* lookup_feats, const float* poses, const float* K,
+                               const float* inv_K, const float* depth_bins, int B, int F, int C, int D, int h, int w,
+                               float eps, int set_missing_to_max, float* cost_volume, float* missing_mask,
+                               float* masked_cost_volume, float* lowest_cost, float* confidence_mask, void* stream) {
+  const int st0 = costvol_shape_status(B, F, C, D, h, w);
+  if (st0 != MAL_OK) return st0;
+  if (!current_feats || !lookup_feats || !poses || !K || !inv_K || !depth_bins || !cost_volume) return MAL_EINVAL;
+  const CostVolParams p = costvol_params(current_feats, lookup_feats, poses, K, inv_K, depth_bins, B, F, D, h, w, eps,
+                                         set_missing_to_max, cost_volume, missing_mask, masked_cost_volume, lowest_cost,
+                                         confidence_mask);
   hipStream_t st = (hipStream_t)stream;
   if (g_costvol_impl == 0)
     hipLaunchKernelGGL(costvol_match_kernel, dim3((w + 3) / 4, h, B), dim3(256), 0, st, p);
@@ -661,9 +606,9 @@ extern "C" int mal_cost_volume(const float* current_feats, const float* lookup_f
 static size_t dyn_occ_bytes(int B, int F) { return (((size_t)B * F * kOccH * kOccW) + 255) / 256 * 256; }
 
 static int dyn_shape_status(int B, int F, int C, int D, int h, int w) {
-  if (B <= 0 || F <= 0 || D <= 0 || h < 5 || w < 5) return MAL_ESHAPE;
-  if (C != kCvC || D > 256 || B > 65535 || (long long)B * F > 65535) return MAL_ESHAPE;
-  if ((double)B * D * h * w > 2.0e9 / 4 || (double)B * F * h * w * C > 2.0e9 / 4) return MAL_ESHAPE;
+  const int st = costvol_shape_status(B, F, C, D, h, w);
+  if (st != MAL_OK) return st;
+  if (B > 65535 || (long long)B * F > 65535) return MAL_ESHAPE;  // grid dimensions z (B) and of the occlusion launches (B*F)
   return MAL_OK;
 }
 
@@ -690,10 +635,8 @@ extern "C" int mal_cost_volume_dyn(const float* current_feats, const float* look
   }
   CostVolDynParams q = {};
   CostVolParams& p = q.cv;
-  p.cur = current_feats; p.look = lookup_feats; p.poses = poses; p.K = K; p.invK = inv_K; p.bins = depth_bins;
-  p.B = B; p.F = F; p.D = D; p.h = h; p.w = w; p.eps = eps; p.set_missing_to_max = set_missing_to_max;
-  p.cost = cost_volume; p.missing = missing_mask; p.masked = masked_cost_volume; p.lowest_cost = lowest_cost;
-  p.confidence = confidence_mask;
+  p = costvol_params(current_feats, lookup_feats, poses, K, inv_K, depth_bins, B, F, D, h, w, eps, set_missing_to_max,
+                     cost_volume, missing_mask, masked_cost_volume, lowest_cost, confidence_mask);
   q.images = lookup_images; q.aug = aug_mask; q.H = H; q.W = W;
   q.pool_th = pool_th;
   q.occ = (unsigned char*)ws; q.m = occ ? (unsigned char*)ws + dyn_occ_bytes(B, F) : nullptr;

@@ -13,6 +13,7 @@
 //                       scheme as the cost volume's match kernel, mal_costvol.hip).
 #include "mal_common.h"
 #include "mal_device.h"
+#include "mal_sample.h"
 
 namespace mal {
 
@@ -98,6 +99,28 @@ __global__ __launch_bounds__(256) void epi_coords_of_depths_kernel(const float* 
   coords[o + (size_t)D * hw] = fy * (X1[1] * d) + cy;
 }
 
+// The sampling position (in elements of a pyramid level of size hl x wl) of pixel coordinates (u, v) of the (h,w) map:
+// corr.py:38-39 / utils.py:374-379, then grid_sample's unnormalise for align_corners=False on the level's size
+MAL_DEV void level_position(float u, float v, int w, int h, int wl, int hl, float& ix, float& iy) {
+  const float gx = div_(2.0f * (u + 0.5f), (float)w) - 1.0f, gy = div_(2.0f * (v + 0.5f), (float)h) - 1.0f;
+  ix = ((gx + 1.0f) * (float)wl - 1.0f) / 2.0f; iy = ((gy + 1.0f) * (float)hl - 1.0f) / 2.0f;
+}
+
+// The zero-padded bilinear taps at that position (mal_sample.h): ELEMENT offsets, clamped into the map, weights zeroed where
+// padding; the fractions and validity bits travel along for the VJPs.  Callers that walk channel planes keep o[k] * 4u.
+struct LevelTaps { unsigned o[4]; float w[4]; Frac f; bool v[4]; };
+MAL_DEV LevelTaps level_taps(float u, float v, int w, int h, int wl, int hl) {
+  LevelTaps t;
+  float ix, iy;
+  level_position(u, v, w, h, wl, hl, ix, iy);
+  const Corners c = corners_of(ix, iy, wl, hl);
+  t.f = frac_next_minus(ix, iy, c);
+  tap_weights(c, t.f, t.w);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { t.o[k] = (unsigned)c.o[k]; t.v[k] = c.v[k]; }
+  return t;
+}
+
 struct EpiSampleParams {
   const float* fmap1; const float* f2[kEpiMaxLevels];
   const float* coords;
@@ -124,23 +147,9 @@ __global__ __launch_bounds__(256) void epi_sample_kernel(EpiSampleParams p) {
   for (int g = 0; g < kEpiG; ++g) {
     const int s = level * p.d1 + min(j0 + g, p.d1 - 1);
     const size_t o = ((size_t)b * 2 * D + s) * hw + pix;
-    const float u = p.coords[o], v = p.coords[o + (size_t)D * hw];
-    // corr.py:38-39 then grid_sample's unnormalise for align_corners=False on the level's size
-    const float gx = div_(2.0f * (u + 0.5f), (float)p.w) - 1.0f, gy = div_(2.0f * (v + 0.5f), (float)p.h) - 1.0f;
-    const float ix = ((gx + 1.0f) * (float)wl - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)hl - 1.0f) / 2.0f;
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float xc = fminf(fmaxf(x0f, -2.0f), (float)wl + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)hl + 1.0f);
-    const bool wild = !(x0f == xc && y0f == yc);  // far outside (or NaN): every tap is padding
-    const int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
-    const float tx = ix - x0f, ty = iy - y0f, ex = (x0f + 1.0f) - ix, ey = (y0f + 1.0f) - iy;
-    const bool vx0 = x0 >= 0 && x0 < wl, vx1 = x1 >= 0 && x1 < wl, vy0 = y0 >= 0 && y0 < hl, vy1 = y1 >= 0 && y1 < hl;
-    const int cx0 = min(max(x0, 0), wl - 1), cx1 = min(max(x1, 0), wl - 1), cy0 = min(max(y0, 0), hl - 1), cy1 = min(max(y1, 0), hl - 1);
-    off[g][0] = (unsigned)(cy0 * wl + cx0) * 4u; off[g][1] = (unsigned)(cy0 * wl + cx1) * 4u;
-    off[g][2] = (unsigned)(cy1 * wl + cx0) * 4u; off[g][3] = (unsigned)(cy1 * wl + cx1) * 4u;
-    wt[g][0] = (!wild && vx0 && vy0) ? ex * ey : 0.f;
-    wt[g][1] = (!wild && vx1 && vy0) ? tx * ey : 0.f;
-    wt[g][2] = (!wild && vx0 && vy1) ? ex * ty : 0.f;
-    wt[g][3] = (!wild && vx1 && vy1) ? tx * ty : 0.f;
+    const LevelTaps t = level_taps(p.coords[o], p.coords[o + (size_t)D * hw], p.w, p.h, wl, hl);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { off[g][k] = t.o[k] * 4u; wt[g][k] = t.w[k]; }
   }
   const int cg = p.C / p.heads;  // channels per head
   const float inv_cg = 1.0f / (float)cg;
@@ -153,15 +162,7 @@ __global__ __launch_bounds__(256) void epi_sample_kernel(EpiSampleParams p) {
       const float f1 = p.fmap1[((size_t)b * p.C + c) * hw + pix];
       const char* pl = reinterpret_cast<const char*>(f2l + ((size_t)b * p.C + c) * hwl);
 #pragma unroll
-      for (int g = 0; g < kEpiG; ++g) {
-        const float a = *reinterpret_cast<const float*>(pl + off[g][0]), bb = *reinterpret_cast<const float*>(pl + off[g][1]);
-        const float cc = *reinterpret_cast<const float*>(pl + off[g][2]), d = *reinterpret_cast<const float*>(pl + off[g][3]);
-        float o = a * wt[g][0];
-        o = fma_(bb, wt[g][1], o);
-        o = fma_(cc, wt[g][2], o);
-        o = fma_(d, wt[g][3], o);
-        sum[g] += fabsf(f1 - o);
-      }
+      for (int g = 0; g < kEpiG; ++g) sum[g] += fabsf(f1 - plane_sample(pl, off[g], wt[g]));
     }
 #pragma unroll
     for (int g = 0; g < kEpiG; ++g) {
@@ -308,22 +309,12 @@ __global__ __launch_bounds__(256) void epi_sample_bwd_kernel(EpiSampleBwdParams 
     act[g] = live && j0 + g < p.d1;
     const int s = level * p.d1 + min(j0 + g, p.d1 - 1);
     const size_t o = ((size_t)b * 2 * D + s) * hw + pix;
-    const float u = p.coords[o], v = p.coords[o + (size_t)D * hw];
-    const float gx = div_(2.0f * (u + 0.5f), (float)p.w) - 1.0f, gy = div_(2.0f * (v + 0.5f), (float)p.h) - 1.0f;
-    const float ix = ((gx + 1.0f) * (float)wl - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)hl - 1.0f) / 2.0f;
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float xc = fminf(fmaxf(x0f, -2.0f), (float)wl + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)hl + 1.0f);
-    const bool wild = !(x0f == xc && y0f == yc);
-    const int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
-    const float tx = ix - x0f, ty = iy - y0f, ex = (x0f + 1.0f) - ix, ey = (y0f + 1.0f) - iy;
-    const bool vx0 = x0 >= 0 && x0 < wl, vx1 = x1 >= 0 && x1 < wl, vy0 = y0 >= 0 && y0 < hl, vy1 = y1 >= 0 && y1 < hl;
-    const int cx0 = min(max(x0, 0), wl - 1), cx1 = min(max(x1, 0), wl - 1), cy0 = min(max(y0, 0), hl - 1), cy1 = min(max(y1, 0), hl - 1);
-    off[g][0] = (unsigned)(cy0 * wl + cx0) * 4u; off[g][1] = (unsigned)(cy0 * wl + cx1) * 4u;
-    off[g][2] = (unsigned)(cy1 * wl + cx0) * 4u; off[g][3] = (unsigned)(cy1 * wl + cx1) * 4u;
-    const bool v00 = !wild && vx0 && vy0, v10 = !wild && vx1 && vy0, v01 = !wild && vx0 && vy1, v11 = !wild && vx1 && vy1;
-    wt[g][0] = v00 ? ex * ey : 0.f; wt[g][1] = v10 ? tx * ey : 0.f; wt[g][2] = v01 ? ex * ty : 0.f; wt[g][3] = v11 ? tx * ty : 0.f;
-    dwx[g][0] = v00 ? -ey : 0.f; dwx[g][1] = v10 ? ey : 0.f; dwx[g][2] = v01 ? -ty : 0.f; dwx[g][3] = v11 ? ty : 0.f;
-    dwy[g][0] = v00 ? -ex : 0.f; dwy[g][1] = v10 ? -tx : 0.f; dwy[g][2] = v01 ? ex : 0.f; dwy[g][3] = v11 ? tx : 0.f;
+    const LevelTaps t = level_taps(p.coords[o], p.coords[o + (size_t)D * hw], p.w, p.h, wl, hl);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { off[g][k] = t.o[k] * 4u; wt[g][k] = t.w[k]; }
+    const Frac& f = t.f;
+    dwx[g][0] = t.v[0] ? -f.ey : 0.f; dwx[g][1] = t.v[1] ? f.ey : 0.f; dwx[g][2] = t.v[2] ? -f.ty : 0.f; dwx[g][3] = t.v[3] ? f.ty : 0.f;
+    dwy[g][0] = t.v[0] ? -f.ex : 0.f; dwy[g][1] = t.v[1] ? -f.tx : 0.f; dwy[g][2] = t.v[2] ? f.ex : 0.f; dwy[g][3] = t.v[3] ? f.tx : 0.f;
   }
   const int cg = p.C / p.heads;
   const float inv_cg = 1.0f / (float)cg;
@@ -346,13 +337,8 @@ __global__ __launch_bounds__(256) void epi_sample_bwd_kernel(EpiSampleBwdParams 
       float g_f1 = 0.f;
 #pragma unroll
       for (int g = 0; g < kEpiG; ++g) {
-        const float a = *reinterpret_cast<const float*>(pl + off[g][0]), bb = *reinterpret_cast<const float*>(pl + off[g][1]);
-        const float cc = *reinterpret_cast<const float*>(pl + off[g][2]), d = *reinterpret_cast<const float*>(pl + off[g][3]);
-        float o = a * wt[g][0];
-        o = fma_(bb, wt[g][1], o);
-        o = fma_(cc, wt[g][2], o);
-        o = fma_(d, wt[g][3], o);
-        const float df = f1 - o;
+        const float a = tap_load(pl, off[g][0]), bb = tap_load(pl, off[g][1]), cc = tap_load(pl, off[g][2]), d = tap_load(pl, off[g][3]);
+        const float df = f1 - blend4(a, bb, cc, d, wt[g]);
         const float k = go[g] * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));  // d |f1 - o| / d f1, times the cotangent
         g_f1 += k;
         g_ix[g] -= k * (((a * dwx[g][0] + bb * dwx[g][1]) + cc * dwx[g][2]) + d * dwx[g][3]);
@@ -390,27 +376,6 @@ __global__ __launch_bounds__(256) void epi_sample_bwd_kernel(EpiSampleBwdParams 
 // and integer addition is associative, so this sum does not depend on the order either.  The global-atomic scatter
 // above ran at 36 G lane-adds/s (1.6 G of them at DualRefine's size: 44 ms) and float LDS adds at 216 G/s (7.4 ms); it
 // remains the path for planes that do not fit the LDS (48x160 + 24x80 + 12x40 accumulators = 79 KB of the 160).
-struct LevelTaps { unsigned o[4]; float w[4]; };
-MAL_DEV LevelTaps level_taps(float u, float v, int w, int h, int wl, int hl) {
-  LevelTaps t;
-  const float gx = div_(2.0f * (u + 0.5f), (float)w) - 1.0f, gy = div_(2.0f * (v + 0.5f), (float)h) - 1.0f;
-  const float ix = ((gx + 1.0f) * (float)wl - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)hl - 1.0f) / 2.0f;
-  const float x0f = floorf(ix), y0f = floorf(iy);
-  const float xc = fminf(fmaxf(x0f, -2.0f), (float)wl + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)hl + 1.0f);
-  const bool wild = !(x0f == xc && y0f == yc);
-  const int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
-  const float tx = ix - x0f, ty = iy - y0f, ex = (x0f + 1.0f) - ix, ey = (y0f + 1.0f) - iy;
-  const bool vx0 = x0 >= 0 && x0 < wl, vx1 = x1 >= 0 && x1 < wl, vy0 = y0 >= 0 && y0 < hl, vy1 = y1 >= 0 && y1 < hl;
-  const int cx0 = min(max(x0, 0), wl - 1), cx1 = min(max(x1, 0), wl - 1), cy0 = min(max(y0, 0), hl - 1), cy1 = min(max(y1, 0), hl - 1);
-  t.o[0] = (unsigned)(cy0 * wl + cx0); t.o[1] = (unsigned)(cy0 * wl + cx1);
-  t.o[2] = (unsigned)(cy1 * wl + cx0); t.o[3] = (unsigned)(cy1 * wl + cx1);
-  t.w[0] = (!wild && vx0 && vy0) ? ex * ey : 0.f;
-  t.w[1] = (!wild && vx1 && vy0) ? tx * ey : 0.f;
-  t.w[2] = (!wild && vx0 && vy1) ? ex * ty : 0.f;
-  t.w[3] = (!wild && vx1 && vy1) ? tx * ty : 0.f;
-  return t;
-}
-
 constexpr int kPlaneThreads = 512;
 constexpr float kFixOne = 1073741824.0f;  // 2^30
 MAL_DEV void fix_add(unsigned long long* cell, float v, float to_fix) {
@@ -486,12 +451,7 @@ __global__ __launch_bounds__(THREADS) void epi_sample_bwd_planes_kernel(EpiSampl
           go_prev = go;
           float smp;
           if (p.probe & 4) smp = u * t.w[0];  // experiment: no gathers
-          else {
-            smp = pl[k][t.o[0]] * t.w[0];
-            smp = fma_(pl[k][t.o[1]], t.w[1], smp);
-            smp = fma_(pl[k][t.o[2]], t.w[2], smp);
-            smp = fma_(pl[k][t.o[3]], t.w[3], smp);
-          }
+          else smp = blend4(pl[k][t.o[0]], pl[k][t.o[1]], pl[k][t.o[2]], pl[k][t.o[3]], t.w);
           const float df = f1[k] - smp;
           const float kk = go * (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
           g_f1[k] += kk;
@@ -586,37 +546,15 @@ MAL_DEV float robust_weight(float cost, float u, float v, int h, int w, float* d
   return valid ? wl : 0.f;
 }
 
-struct Tap4 { unsigned o[4]; float w[4]; float tx, ty, ex, ey; bool v[4]; };  // v: tap inside the map (and the position sane)
-
-// bilinear, zero-padded, align_corners=False sample position (u, v) in pixels of an (h,w) map (corr.py:38-39 /
-// utils.py:374-379 + grid_sample's unnormalise)
+// the taps of the pose-refinement step: level_taps on the (h,w) map itself, with BYTE offsets for plane_sample
+using Tap4 = LevelTaps;
 MAL_DEV Tap4 taps_at(float u, float v, int h, int w) {
-  Tap4 t;
-  const float gx = div_(2.0f * (u + 0.5f), (float)w) - 1.0f, gy = div_(2.0f * (v + 0.5f), (float)h) - 1.0f;
-  const float ix = ((gx + 1.0f) * (float)w - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)h - 1.0f) / 2.0f;
-  const float x0f = floorf(ix), y0f = floorf(iy);
-  const float xc = fminf(fmaxf(x0f, -2.0f), (float)w + 1.0f), yc = fminf(fmaxf(y0f, -2.0f), (float)h + 1.0f);
-  const bool wild = !(x0f == xc && y0f == yc);
-  const int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
-  const float tx = ix - x0f, ty = iy - y0f, ex = (x0f + 1.0f) - ix, ey = (y0f + 1.0f) - iy;
-  const bool vx0 = x0 >= 0 && x0 < w, vx1 = x1 >= 0 && x1 < w, vy0 = y0 >= 0 && y0 < h, vy1 = y1 >= 0 && y1 < h;
-  const int cx0 = min(max(x0, 0), w - 1), cx1 = min(max(x1, 0), w - 1), cy0 = min(max(y0, 0), h - 1), cy1 = min(max(y1, 0), h - 1);
-  t.o[0] = (unsigned)(cy0 * w + cx0) * 4u; t.o[1] = (unsigned)(cy0 * w + cx1) * 4u;
-  t.o[2] = (unsigned)(cy1 * w + cx0) * 4u; t.o[3] = (unsigned)(cy1 * w + cx1) * 4u;
-  t.v[0] = !wild && vx0 && vy0; t.v[1] = !wild && vx1 && vy0; t.v[2] = !wild && vx0 && vy1; t.v[3] = !wild && vx1 && vy1;
-  t.w[0] = t.v[0] ? ex * ey : 0.f;
-  t.w[1] = t.v[1] ? tx * ey : 0.f;
-  t.w[2] = t.v[2] ? ex * ty : 0.f;
-  t.w[3] = t.v[3] ? tx * ty : 0.f;
-  t.tx = tx; t.ty = ty; t.ex = ex; t.ey = ey;
+  Tap4 t = level_taps(u, v, w, h, w, h);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t.o[k] *= 4u;
   return t;
 }
-MAL_DEV float sample4(const char* plane, const Tap4& t) {
-  float o = *reinterpret_cast<const float*>(plane + t.o[0]) * t.w[0];
-  o = fma_(*reinterpret_cast<const float*>(plane + t.o[1]), t.w[1], o);
-  o = fma_(*reinterpret_cast<const float*>(plane + t.o[2]), t.w[2], o);
-  return fma_(*reinterpret_cast<const float*>(plane + t.o[3]), t.w[3], o);
-}
+MAL_DEV float plane_sample(const char* plane, const Tap4& t) { return plane_sample(plane, t.o, t.w); }
 
 // PoseUpdate.direct_align up to the solve (utils.py:303-355, without --robust_pose_loss).  The reference materialises
 // J = -J_img J_pix (B,hw,C,6) and a 6x6 matrix per pixel; with J_c = -(gx_c a + gy_c b) (a, b: the two rows of the
@@ -639,14 +577,14 @@ __global__ __launch_bounds__(256) void epi_align_kernel(EpiAlignParams p) {
 #pragma unroll 2
   for (int c = 0; c < p.C; ++c) {
     const char* pl = reinterpret_cast<const char*>(p.tgt + ((size_t)b * p.C + c) * hw);
-    const float f0 = sample4(pl, t[0]);
-    const float gx = (sample4(pl, t[1]) - sample4(pl, t[2])) / 2.0f, gy = (sample4(pl, t[3]) - sample4(pl, t[4])) / 2.0f;
+    const float f0 = plane_sample(pl, t[0]);
+    const float gx = (plane_sample(pl, t[1]) - plane_sample(pl, t[2])) / 2.0f, gy = (plane_sample(pl, t[3]) - plane_sample(pl, t[4])) / 2.0f;
     const float r = p.src[((size_t)b * p.C + c) * hw + pix] - f0;
     Sxx = fma_(gx, gx, Sxx); Sxy = fma_(gx, gy, Sxy); Syy = fma_(gy, gy, Syy);
     Srx = fma_(r, gx, Srx); Sry = fma_(r, gy, Sry);
     cost = fma_(r, r, cost);
   }
-  float wgt = p.src_w[(size_t)b * hw + pix] * sample4(reinterpret_cast<const char*>(p.tgt_w + (size_t)b * hw), t[0]);
+  float wgt = p.src_w[(size_t)b * hw + pix] * plane_sample(reinterpret_cast<const char*>(p.tgt_w + (size_t)b * hw), t[0]);
   if (p.weight) wgt *= p.weight[(size_t)b * hw + pix];
   if (p.robust) {
     float unused;
@@ -806,15 +744,15 @@ __global__ __launch_bounds__(256) void epi_align_bwd_kernel(EpiAlignParams p) {
 #pragma unroll 2
   for (int c = 0; c < p.C; ++c) {
     const char* pl = reinterpret_cast<const char*>(p.tgt + ((size_t)b * p.C + c) * hw);
-    const float f0 = sample4(pl, t[0]);
-    const float gx = (sample4(pl, t[1]) - sample4(pl, t[2])) / 2.0f, gy = (sample4(pl, t[3]) - sample4(pl, t[4])) / 2.0f;
+    const float f0 = plane_sample(pl, t[0]);
+    const float gx = (plane_sample(pl, t[1]) - plane_sample(pl, t[2])) / 2.0f, gy = (plane_sample(pl, t[3]) - plane_sample(pl, t[4])) / 2.0f;
     const float r = p.src[((size_t)b * p.C + c) * hw + pix] - f0;
     Sxx = fma_(gx, gx, Sxx); Sxy = fma_(gx, gy, Sxy); Syy = fma_(gy, gy, Syy);
     Srx = fma_(r, gx, Srx); Sry = fma_(r, gy, Sry);
     cost = fma_(r, r, cost);
   }
   const char* twp = reinterpret_cast<const char*>(p.tgt_w + (size_t)b * hw);
-  const float sw = p.src_w[(size_t)b * hw + pix], tw = sample4(twp, t[0]);
+  const float sw = p.src_w[(size_t)b * hw + pix], tw = plane_sample(twp, t[0]);
   const float wt = p.weight ? p.weight[(size_t)b * hw + pix] : 1.0f;
   float rw = 1.0f, drw_dcost = 0.f;
   if (p.robust) rw = robust_weight(cost, uu[0], vv[0], p.h, p.w, &drw_dcost);
@@ -877,8 +815,8 @@ __global__ __launch_bounds__(256) void epi_align_bwd_kernel(EpiAlignParams p) {
     const float v01 = tp.v[1] ? *reinterpret_cast<const float*>(plane + tp.o[1]) : 0.f;
     const float v10 = tp.v[2] ? *reinterpret_cast<const float*>(plane + tp.o[2]) : 0.f;
     const float v11 = tp.v[3] ? *reinterpret_cast<const float*>(plane + tp.o[3]) : 0.f;
-    *dix = (v01 - v00) * tp.ey + (v11 - v10) * tp.ty;
-    *diy = (v10 - v00) * tp.ex + (v11 - v01) * tp.tx;
+    *dix = (v01 - v00) * tp.f.ey + (v11 - v10) * tp.f.ty;
+    *diy = (v10 - v00) * tp.f.ex + (v11 - v01) * tp.f.tx;
   };
   auto scatter = [&](float* plane, const Tap4& tp, float g) {
 #pragma unroll
@@ -894,8 +832,8 @@ __global__ __launch_bounds__(256) void epi_align_bwd_kernel(EpiAlignParams p) {
   for (int c = 0; c < p.C; ++c) {
     const size_t po = ((size_t)b * p.C + c) * hw;
     const char* pl = reinterpret_cast<const char*>(p.tgt + po);
-    const float f0 = sample4(pl, t[0]);
-    const float gx = (sample4(pl, t[1]) - sample4(pl, t[2])) / 2.0f, gy = (sample4(pl, t[3]) - sample4(pl, t[4])) / 2.0f;
+    const float f0 = plane_sample(pl, t[0]);
+    const float gx = (plane_sample(pl, t[1]) - plane_sample(pl, t[2])) / 2.0f, gy = (plane_sample(pl, t[3]) - plane_sample(pl, t[4])) / 2.0f;
     const float r = p.src[po + pix] - f0;
     const float dgx = (2.0f * gx * dSxx + gy * dSxy) + r * dSrx, dgy = (2.0f * gy * dSyy + gx * dSxy) + r * dSry;
     const float dr = (gx * dSrx + gy * dSry) + 2.0f * r * dcost;
@@ -940,8 +878,8 @@ __global__ __launch_bounds__(kPlaneThreads) void epi_align_bwd_planes_kernel(Epi
       float cf[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) cf[k] = p.coef[((size_t)b * 6 + k) * hw + pix];
-      const float f0 = sample4(pl, t[0]);
-      const float gx = (sample4(pl, t[1]) - sample4(pl, t[2])) / 2.0f, gy = (sample4(pl, t[3]) - sample4(pl, t[4])) / 2.0f;
+      const float f0 = plane_sample(pl, t[0]);
+      const float gx = (plane_sample(pl, t[1]) - plane_sample(pl, t[2])) / 2.0f, gy = (plane_sample(pl, t[3]) - plane_sample(pl, t[4])) / 2.0f;
       const float r = p.src[po + pix] - f0;
       const float dgx = (2.0f * gx * cf[0] + gy * cf[1]) + r * cf[3], dgy = (2.0f * gy * cf[2] + gx * cf[1]) + r * cf[4];
       const float dr = (gx * cf[3] + gy * cf[4]) + 2.0f * r * cf[5];

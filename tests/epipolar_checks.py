@@ -270,6 +270,64 @@ def run_lookup(c, terms=("corr", "ds", "max_dx"), need=LEAVES):
     return out, {k: (None if v.grad is None else v.grad.cpu()) for k, v in lv.items()}
 
 
+# ---------------------------------------------------------------- the corner table (csrc/mal_sample.h)
+# The lookup takes its coordinates as an input, so sampling positions can be placed exactly: h and w are powers of two, one
+# level, so the position in elements IS the coordinate (2 (x + 0.5) / 8 - 1 and back are exact).  x runs along the hypothesis
+# axis, one call per y: on and next to every bound of the corner code -- the first and last column / row, -1 and size (the
+# outermost floor with no tap inside), one float inside them, far outside (the clamp of the int conversion).
+CORNER_SHAPE = (1, 4, 4, 8)  # B, C, h, w; one level, one head
+CORNER_X = (-1.5, -1.0, -0.5, -2.0 ** -20, 0.0, 0.25, 3.0, 6.5, 7.0, 7.0 + 2.0 ** -20, 7.5, 8.0, 1e4, -1e4, 1e30)
+CORNER_Y = (-1.5, -1.0, -0.5, 0.0, 1.5, 3.0, 3.5, 4.0, 1e30)
+CORNER_WILD_X = (float("nan"), float("inf"))  # held to the all-padding property only, not to the oracle
+
+
+def all_padding(x, y):
+    """every tap of the position is padding or carries a weight of exactly zero: the sample is 0 and nothing reaches fmap2"""
+    B, C, h, w = CORNER_SHAPE
+    return x != x or y != y or x <= -1 or x >= w or y <= -1 or y >= h
+
+
+def corner_case(y, xs=CORNER_X):
+    """-> f1, f2 (fp16-representable), coords (1,2,1,len(xs),h,w) with x = xs[j] and y everywhere, a cotangent that is
+    non-zero on the all-padding hypotheses only, and a cotangent that is non-zero everywhere"""
+    B, C, h, w = CORNER_SHAPE
+    g = torch.Generator().manual_seed(4242)
+    f1, f2 = (torch.randn(B, C, h, w, generator=g).half().float() for _ in range(2))
+    coords = torch.empty(B, 2, 1, len(xs), h, w)
+    coords[:, 0, 0] = torch.tensor(xs, dtype=torch.float32)[None, :, None, None]
+    coords[:, 1, 0] = y
+    w_all = 0.5 + torch.rand(B, len(xs), h, w, generator=g)
+    pad = torch.tensor([all_padding(x, y) for x in xs])
+    return dict(f1=f1, f2=f2, coords=coords, pad=pad, w_pad=w_all * pad[None, :, None, None], w_all=w_all)
+
+
+def corner_oracle(c, dtype, cot="w_all"):
+    """-> (corr, d <corr, cotangent> / d f2) of oracle.epi_oracle.coord_sample in ``dtype``"""
+    f2 = c["f2"].to(dtype).clone().requires_grad_(True)
+    corr = E.coord_sample(c["f1"].to(dtype), [f2], c["coords"].to(dtype), 1, 1)
+    (corr * c[cot].to(dtype)).sum().backward()
+    return corr.detach(), f2.grad
+
+
+def mean_abs_f1(c):
+    """mean |fmap1| over the four channels as the kernel sums them: in channel order, in fp32 (exact here: fp16 inputs)"""
+    a = c["f1"].abs()
+    return (((a[:, 0] + a[:, 1]) + a[:, 2]) + a[:, 3]) * 0.25
+
+
+def run_corner(c, cot):
+    """the device's lookup at the case's coordinates -> (corr, d <corr, c[cot]> / d f2)"""
+    from mal_amd import epipolar
+    d = lambda t: t.to(DEV)
+    f2 = d(c["f2"]).clone().requires_grad_(True)
+    S = epipolar.CoordSampler(_args(2, 1))
+    S.register(d(c["f1"]), f2, num_levels=1)
+    corr = S(d(c["coords"]), 1, 1)
+    (corr * d(c[cot])).sum().backward()
+    torch.cuda.synchronize()
+    return corr.detach().cpu(), f2.grad.cpu()
+
+
 # ---------------------------------------------------------------- pose refinement, piecewise
 def oracle_gradcoords(i, dtype, w_cp=None, w_P2=None):
     """depth2gradcoords and the gradients of <c_p, w_cp> + <P2, w_P2> (either may be None) w.r.t. depth and poses"""

@@ -68,6 +68,37 @@ def test_align_case_is_admissible(name, robust):
         assert valid[:2].all() and not valid[2:4].any()
 
 
+@pytest.mark.parametrize("y", X.CORNER_Y)
+def test_corner_table_is_admissible(y):
+    """the table of tests/test_gpu_epipolar_sweep.py::test_corner_table: the oracle is finite on it, its fp32 form is inside
+    the gate's floor, and a hypothesis gives exactly mean |fmap1| -- and sends exactly nothing to fmap2 -- where
+    ``all_padding`` says so and nowhere else"""
+    c = X.corner_case(y)
+    (o64, g64), (o32, g32) = (X.corner_oracle(c, dt) for dt in (torch.float64, torch.float32))
+    assert torch.isfinite(o64).all() and torch.isfinite(o32).all() and torch.isfinite(g64).all()
+    X.admissible(dict(corr=o64), dict(corr=o32), forward=True, what="corner y=%g" % y)
+    want = X.mean_abs_f1(c)
+    for j, x in enumerate(X.CORNER_X):
+        for o in (o64, o32):
+            assert bool(torch.equal(o[:, j], want.to(o.dtype))) == X.all_padding(x, y), (x, y)
+    assert torch.equal(c["pad"], torch.tensor([X.all_padding(x, y) for x in X.CORNER_X]))
+    for dt in (torch.float64, torch.float32):
+        assert not X.corner_oracle(c, dt, "w_pad")[1].abs().max() > 0
+        if not c["pad"].all():
+            assert float(g64.abs().max()) > 0
+
+
+def test_corner_table_meets_every_bound_of_the_corner_code():
+    B, C, h, w = X.CORNER_SHAPE
+    for vals, size in ((X.CORNER_X, w), (X.CORNER_Y, h)):
+        fl = {float(np.floor(np.float32(v))) for v in vals}
+        assert {-2.0, -1.0, 0.0, size - 1.0, float(size)} <= fl          # every floor around both edges
+        assert any(v > size + 1 for v in vals)                          # past the clamp of the int conversion
+        assert any(-1 < v < 0 for v in vals) and any(size - 1 < v < size for v in vals)  # one tap in, one out, both weighted
+    assert any(v < -2 for v in X.CORNER_X)                               # below the clamp
+    assert all(X.all_padding(x, 0.0) for x in X.CORNER_WILD_X)
+
+
 def test_every_lds_band_is_covered():
     """the lookup's backward picks two planes / one plane / the atomic scatter by comparing lds and 2 lds with the limit the
     device reports (160 KB on gfx950; 64 KB where raising it fails), the align step's by comparing h w 8: with a case in

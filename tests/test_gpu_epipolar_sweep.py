@@ -100,6 +100,54 @@ def test_every_subset_of_leaves(name):
                     assert torch.equal(grads[k], full[k]), (groups, k)
 
 
+# ---------------------------------------------------------------- the corner table
+_CORNER = {}
+
+
+def _corner(y):
+    if y not in _CORNER:
+        c = X.corner_case(y)
+        _CORNER[y] = (c, X.corner_oracle(c, torch.float64)[0], X.corner_oracle(c, torch.float32)[0])
+    return _CORNER[y]
+
+
+@pytest.mark.parametrize("y", X.CORNER_Y)
+def test_corner_table(y):
+    """positions on and next to every bound of the shared corner code (csrc/mal_sample.h), placed exactly through the
+    lookup's coordinate input: the forward under the sweep's gate; a hypothesis whose taps are all padding gives exactly
+    mean |fmap1| and sends exactly nothing to fmap2, under each backward formulation.  Coordinate gradients are not
+    compared: on a tap boundary the slope is one-sided (epipolar_checks)."""
+    from tests.test_gpu_schedule import get_option, set_options
+    c, o64, o32 = _corner(y)
+    corr, g_all = X.run_corner(c, "w_all")
+    print("corner y=%g" % y, X.check(dict(corr=corr), dict(corr=o64), dict(corr=o32), forward=True, what="corner y=%g" % y))
+    want = X.mean_abs_f1(c)
+    for j, x in enumerate(X.CORNER_X):
+        if X.all_padding(x, y):
+            assert torch.equal(corr[:, j], want), (x, y)
+    assert c["pad"].all() or float(g_all.abs().max()) > 0
+    saved = get_option("epi_bwd_planes")
+    try:
+        for planes in (0, 1, 2):
+            set_options(epi_bwd_planes=planes)
+            g_pad = X.run_corner(c, "w_pad")[1]
+            assert torch.equal(g_pad, torch.zeros_like(g_pad)), (y, planes)
+    finally:
+        set_options(epi_bwd_planes=saved)
+
+
+@pytest.mark.parametrize("y", X.CORNER_Y)
+def test_corner_table_nan_and_inf(y):
+    """x = NaN and x = +inf: all padding, as above; not held to the oracle"""
+    c = X.corner_case(y, X.CORNER_WILD_X)
+    assert c["pad"].all()
+    corr, g_pad = X.run_corner(c, "w_pad")
+    want = X.mean_abs_f1(c)
+    for j in range(len(X.CORNER_WILD_X)):
+        assert torch.equal(corr[:, j], want), (X.CORNER_WILD_X[j], y)
+    assert torch.equal(g_pad, torch.zeros_like(g_pad))
+
+
 # ---------------------------------------------------------------- pose refinement, piecewise
 def _hold_solve_rows(got_o, got_g, o64, g64, rows):
     """the existing per-sample gate of the Cholesky solve (tests/test_gpu_epipolar.py): the conditioning of each 6x6 system"""
